@@ -16,11 +16,15 @@ the `train_step` leg is the C3 optimisation step (full-size encoder fwd+bwd + ra
 bucketed gradient all-reduce over RCCL overlapped with the backward + clip + AdamW) -- the one collective the
 path has, so the 1 -> N curve contains it.
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+A plain run (`python bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, pre-warm, W warm-up
+steps, K timed steps, the outputs of the last timed step if `--dump-outputs DIR` is given, and ONE JSON line (rank 0) with the
+driver's contract (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  `--full` adds everything else to that line:
   "roofline":     live hipEvent timing of the dominant kernel vs the HBM peak, what actually bounds it
   "cpu_baseline": the CPU oracle (a port of the published algorithm; the reference has no CPU rasterizer)
                   on a bounded sample
   "train_step":   M2: C3 ms/step, rendered views/s, bytes all-reduced, RCCL ranks
+  and the stand-alone-loss A/B, the full-outputs and drop-in legs, the C4 / C5 steps and the C2 inference leg
+(the --no-* options below switch single parts of --full off).
 """
 from __future__ import annotations
 
@@ -38,6 +42,7 @@ sys.path.insert(0, str(ROOT))
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s spec (6.3 TB/s achievable)
+DUMP_MAX_ELEMS = 1 << 21   # --dump-outputs: at most 8 MB of float32 per array, so the seven arrays stay under 64 MB
 
 
 def parse(argv=None):
@@ -68,7 +73,17 @@ def parse(argv=None):
     ap.add_argument("--train-tiny", action="store_true", help="small trunk for the train leg (smoke tests only; flagged in the line)")
     ap.add_argument("--dry-cpu", action="store_true",
                     help="launch-path test mode: gloo on CPU, no kernels, no oracle -- checks spawning / sharding / the JSON line")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline and per-stage figures, stand-alone-loss A/B, full-outputs and drop-in legs, train / "
+                         "C4 / C5 / inference legs, CPU baselines (the --no-* options switch single parts off)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy in float32: color, depth, "
+                         "loss_mse, grad_means, grad_covariances, grad_harmonics, grad_opacities; an array of more than "
+                         f"{DUMP_MAX_ELEMS} elements is stored as a fixed seeded sample of that many (flat, in index order)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.dry_cpu:
+        ap.error("--dump-outputs needs the GPU path (--dry-cpu computes nothing)")
+    return args
 
 
 # ------------------------------------------------------------------ launch
@@ -108,6 +123,19 @@ def build_batch(args, rank, dev):
     g = Gaussians(st("means"), st("covariances"), st("harmonics"), st("opacities"))
     cams = dict(extrinsics=st("extrinsics"), intrinsics=st("intrinsics"), near=st("near"), far=st("far"))
     return scenes, g, cams
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <name>.npy in float32; one larger than DUMP_MAX_ELEMS as the same seeded sample of its flat
+    elements in every run, so that two builds can be compared output for output."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))]
+        np.save(out_dir / f"{name}.npy", a)
 
 
 def algorithmic_bytes(stage, V, B, G, P, n_sh, R, R_eff):
@@ -246,6 +274,7 @@ def raster_leg(args, rank, world, dev, dist):
     target = torch.rand((B, Vt, 3, H, W), device=dev, generator=torch.Generator(dev).manual_seed(7 + rank))
     for t in (g.means, g.covariances, g.harmonics, g.opacities):
         t.requires_grad_(True)
+    last = {}
 
     def step():
         for t in (g.means, g.covariances, g.harmonics, g.opacities):
@@ -253,6 +282,8 @@ def raster_leg(args, rank, world, dev, dist):
         # LossMse (src/loss/loss_mse.py:22-31) computed inside the composite kernels (DecoderOutput.loss_mse, round 6)
         out = dec.forward(g, cams["extrinsics"], cams["intrinsics"], cams["near"], cams["far"], (H, W), mse_target=target)
         out.loss_mse.backward()
+        if args.dump_outputs:
+            last["out"] = out
         return out.loss_mse
 
     def step_unfused():       # the round-5 step: decoder, then LossMse as the stand-alone gsr_mse_forward / gsr_mse_backward kernels
@@ -282,34 +313,57 @@ def raster_leg(args, rank, world, dev, dist):
         # Inside the wall-clock-timed region only the two composite kernels (the roofline kernels) are bracketed by hipEvents: every timed stage
         # puts two event records between kernels that otherwise follow each other back to back (~5 us per boundary, ~25 us of a 1.45 ms step with
         # all seven on).  The other five stages are timed right behind it, same workload, in a short pass of their own.
+        # A plain run keeps these two brackets too: its timed region, and so `value`, is the one --full reports.
         prof.set_stages(("composite_fwd", "composite_bwd"))
         rz.PROFILE = prof
         dt = dist_utils.timed_steps(step, args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)
-        stage_ms = prof.read()
-        prof.set_stages(None)
-        for _ in range(min(args.steps, 50)):
-            step()
-        torch.cuda.synchronize(dev)
-        for name, val in prof.read().items():
-            if not name.startswith("composite"):
-                stage_ms[name] = val
-        rz.PROFILE = None
-        # A/B in the same run: the same workload with the loss as two kernels of its own (what `value` was measured on up to round 5)
-        n_ab = min(args.steps, 100)
-        for _ in range(5):
-            step_unfused()
-        torch.cuda.synchronize(dev)
-        t_ab = time.perf_counter()
-        for _ in range(n_ab):
-            step_unfused()
-        torch.cuda.synchronize(dev)
-        unfused = {"ms_per_step": round(1e3 * (time.perf_counter() - t_ab) / n_ab, 4), "steps": n_ab,
-                   "what": "decoder forward, then LossMse as the stand-alone gsr_mse_forward / gsr_mse_backward kernels (the step of rounds 1-5)"}
-        loss_fused, loss_unfused = float(step().item()), float(step_unfused().item())
+        if args.dump_outputs and rank == 0:
+            out = last["out"]
+            dump_outputs(args.dump_outputs, {"color": out.color, "depth": out.depth, "loss_mse": out.loss_mse, "grad_means": g.means.grad,
+                                             "grad_covariances": g.covariances.grad, "grad_harmonics": g.harmonics.grad,
+                                             "grad_opacities": g.opacities.grad})
+        if args.full:
+            stage_ms = prof.read()
+            prof.set_stages(None)
+            for _ in range(min(args.steps, 50)):
+                step()
+            torch.cuda.synchronize(dev)
+            for name, val in prof.read().items():
+                if not name.startswith("composite"):
+                    stage_ms[name] = val
+            rz.PROFILE = None
+            # A/B in the same run: the same workload with the loss as two kernels of its own (what `value` was measured on up to round 5)
+            n_ab = min(args.steps, 100)
+            for _ in range(5):
+                step_unfused()
+            torch.cuda.synchronize(dev)
+            t_ab = time.perf_counter()
+            for _ in range(n_ab):
+                step_unfused()
+            torch.cuda.synchronize(dev)
+            unfused = {"ms_per_step": round(1e3 * (time.perf_counter() - t_ab) / n_ab, 4), "steps": n_ab,
+                       "what": "decoder forward, then LossMse as the stand-alone gsr_mse_forward / gsr_mse_backward kernels (the step of rounds 1-5)"}
+            loss_fused, loss_unfused = float(step().item()), float(step_unfused().item())
     finally:
         gc.enable()
     rz.PROFILE = None
     prof.close()
+    res = {
+        "metric": "256x256 stylized views/sec (fwd+bwd) @ ~65k Gaussians",
+        "value": round(dist_utils.aggregate_throughput(V, args.steps, world, dt), 2), "unit": "views/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"rasterizer fwd+bwd (decoder API + MSE, the loss computed inside the composite kernels): {B} scenes x {Vt} target views/GPU/step, "
+                               f"{H}x{W}, G={G} Gaussians/scene ({args.ctx} ctx view x {args.grid}x{args.grid}), sh_degree="
+                               f"{args.sh_degree}, make_scale_invariant, all views in one batched launch; outputs the decoder discards are not computed "
+                               f"(decoder_splatting_cuda.py:37-68 drops radii / opacity / n_touched, MSE sends no depth gradient: the composite kernels run "
+                               f"their n_touched-free / depth-gradient-free instantiations -- the consumed results are identical)",
+                   "views_per_step_per_gpu": V, "gaussians_per_scene": G, "parallelism": f"dp{world} (scenes sharded)"},
+    }
+    if not args.full:
+        del g, cams, target, dec
+        torch.cuda.empty_cache()
+        return res, scenes
 
     # ---- per-launch algorithmic bytes of every stage (one extra un-timed forward to read R / n_contrib) ----
     rz.KEEP_DEBUG = True
@@ -356,20 +410,8 @@ def raster_leg(args, rank, world, dev, dist):
         "valu_frac": (pf["valu"] or {}).get("valu_active_frac"),
         "alg_bytes_per_launch": cf["alg_bytes"], "avg_launch_ms": cf["avg_ms"], "target_frac": 0.5,
         "note": "SURVEY 8d byte model (44 B per staged entry + 28 B per pixel); the kernel is VALU-issue-bound, DESIGN.md section 6"}
-    res = {
-        "metric": "256x256 stylized views/sec (fwd+bwd) @ ~65k Gaussians",
-        "value": round(dist_utils.aggregate_throughput(V, args.steps, world, dt), 2), "unit": "views/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * dt / args.steps, 4), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"rasterizer fwd+bwd (decoder API + MSE, the loss computed inside the composite kernels): {B} scenes x {Vt} target views/GPU/step, "
-                               f"{H}x{W}, G={G} Gaussians/scene ({args.ctx} ctx view x {args.grid}x{args.grid}), sh_degree="
-                               f"{args.sh_degree}, make_scale_invariant, all views in one batched launch; outputs the decoder discards are not computed "
-                               f"(decoder_splatting_cuda.py:37-68 drops radii / opacity / n_touched, MSE sends no depth gradient: the composite kernels run "
-                               f"their n_touched-free / depth-gradient-free instantiations -- the consumed results are identical)",
-                   "views_per_step_per_gpu": V, "gaussians_per_scene": G, "parallelism": f"dp{world} (scenes sharded)"},
-        "roofline": roofline, "roofline_composite_fwd": roofline_cf,
-        "mse_stand_alone_kernels": dict(unfused, views_per_s=round(V / (unfused["ms_per_step"] * 1e-3), 1), loss=loss_unfused, loss_fused=loss_fused),
-    }
+    res["roofline"], res["roofline_composite_fwd"] = roofline, roofline_cf
+    res["mse_stand_alone_kernels"] = dict(unfused, views_per_s=round(V / (unfused["ms_per_step"] * 1e-3), 1), loss=loss_unfused, loss_fused=loss_fused)
     if rank == 0 and not getattr(args, "no_dropin_leg", False):
         try:
             res["batched_full_outputs"] = full_outputs_leg(args, dev, g, cams, target)
@@ -903,13 +945,13 @@ def main():
                      "spawned_by": "bench.py self-spawn -> torch.distributed.run" if os.environ.get("STYL3R_BENCH_SPAWNED") else
                                    ("torch.distributed.run" if "WORLD_SIZE" in os.environ else "direct"),
                      "device": (torch.cuda.get_device_name(dev) if dev.type == "cuda" else "cpu")}
-    if not args.no_train_leg and not args.dry_cpu:
+    if args.full and not args.no_train_leg and not args.dry_cpu:
         try:
             res["train_step"] = train_leg(args, rank, world, dev, dist)
             res["train_step"]["n_gpus"] = world
         except Exception as e:   # the headline line must survive a failure of the secondary leg; it is reported, not hidden
             res["train_step"] = {"error": f"{type(e).__name__}: {e}"[:400]}
-    if not args.no_stage_legs and not args.no_train_leg and not args.dry_cpu and not args.train_tiny:
+    if args.full and not args.no_stage_legs and not args.no_train_leg and not args.dry_cpu and not args.train_tiny:
         import gc
         for key, config in (("style_stage_step", "c4"), ("stress_512_step", "c5")):
             gc.collect(); torch.cuda.empty_cache()
@@ -917,13 +959,13 @@ def main():
                 res[key] = stage_leg(args, rank, world, dev, dist, config)
             except Exception as e:
                 res[key] = {"error": f"{type(e).__name__}: {e}"[:400]}
-    if rank == 0 and not args.no_infer_leg and not args.dry_cpu:
+    if rank == 0 and args.full and not args.no_infer_leg and not args.dry_cpu:
         try:
             res["infer"] = infer_leg(args, dev)
         except Exception as e:
             res["infer"] = {"error": f"{type(e).__name__}: {e}"[:400]}
     if rank == 0:
-        if not args.no_cpu_baseline and not args.dry_cpu:
+        if args.full and not args.no_cpu_baseline and not args.dry_cpu:
             res["cpu_baseline"] = cpu_baseline(args, scenes)
             if not args.no_train_leg:
                 res["cpu_baseline"]["encoder"] = cpu_encoder_baseline(args)

@@ -7,7 +7,7 @@ timeout 1500 python -m pytest tests/test_gpu_rasterizer.py tests/test_host_bound
 tail -3 $O/${TAG}_raster_tests.log
 GSR_BIN=ballot timeout 1500 python -m pytest tests/test_gpu_rasterizer.py -m gpu -x -q > $O/${TAG}_raster_tests_ballot.log 2>&1
 tail -1 $O/${TAG}_raster_tests_ballot.log
-B="--no-cpu-baseline --no-train-leg --no-infer-leg --no-stage-legs --no-dropin-leg"
+B="--full --no-cpu-baseline --no-train-leg --no-infer-leg --no-stage-legs --no-dropin-leg"
 show() { python - "$1" "$2" <<'PY'
 import json, sys
 try:

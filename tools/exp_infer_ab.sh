@@ -3,7 +3,7 @@
 set -u; TAG=${1:-r06}; O=$PWD/gpurun_out; mkdir -p $O; ROOT=$PWD; rm -f $O/${TAG}_infer_ab.jsonl
 for rep in 1 2; do for T in r05:$ROOT/ab_r05 r06:$ROOT; do
   cd ${T#*:}
-  timeout 900 python bench.py --steps 5 --warmup 2 --prewarm-seconds 0.2 --no-cpu-baseline --no-train-leg --no-stage-legs --no-dropin-leg 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({'tree': '${T%%:*}', 'infer': d.get('infer')}))" >> $O/${TAG}_infer_ab.jsonl
+  timeout 900 python bench.py --full --steps 5 --warmup 2 --prewarm-seconds 0.2 --no-cpu-baseline --no-train-leg --no-stage-legs --no-dropin-leg 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({'tree': '${T%%:*}', 'infer': d.get('infer')}))" >> $O/${TAG}_infer_ab.jsonl
   cd $ROOT
 done; done
 python - <<PY

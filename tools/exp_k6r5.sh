@@ -7,7 +7,7 @@ TAG=${1:-k6r5}; shift; O=gpurun_out; mkdir -p $O
 export TMPDIR=/tmp
 timeout 1500 python -m pytest tests/test_gpu_rasterizer.py tests/test_host_boundary.py -m gpu -x -q > $O/${TAG}_raster_tests.log 2>&1
 tail -3 $O/${TAG}_raster_tests.log
-B="--no-cpu-baseline --no-train-leg --no-infer-leg --no-stage-legs --no-dropin-leg"
+B="--full --no-cpu-baseline --no-train-leg --no-infer-leg --no-stage-legs --no-dropin-leg"
 show() { python - "$1" "$2" <<'PY'
 import json, sys
 try:

@@ -3,8 +3,8 @@
 # path), per-kernel tables of the C3 / C4 / C5 train steps, observed parity distances, the e2e parity tables, every benchmark of DESIGN 6 / 8.
 # (raster kernel stats / timeline / PMC: tools/r06_raster_record.sh)   usage (GPU box): bash tools/r06_round_record.sh <tag>
 set -u; TAG=${1:-r06z}; O=gpurun_out; mkdir -p $O; export TMPDIR=/tmp
-python bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --no-infer-leg --no-stage-legs > $O/${TAG}_bench_torchrun1.json 2> $O/${TAG}_bench_torchrun1.err
+python bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 1 --full --no-infer-leg --no-stage-legs > $O/${TAG}_bench_torchrun1.json 2> $O/${TAG}_bench_torchrun1.err
 for CFG in "c3 10" "c4 6" "c5 1"; do set -- $CFG
   rm -rf /tmp/prof_t; rocprofv3 --kernel-trace -d /tmp/prof_t -- python tools/bench_train.py --config $1 --scenes $2 --steps 3 --warmup 2 --linear-mode f16x3 > /dev/null 2>&1
   python tools/rocpd_timeline.py $(find /tmp/prof_t -name "*.db" | head -1) "k_preprocess<" $O/${TAG}_train_step_$1_b$2_f16x3.md --agg > /dev/null

@@ -12,7 +12,7 @@ for CFG in "c3 10" "c4 6"; do
   rocprofv3 --kernel-trace -d /tmp/prof_$1 -- python tools/bench_train.py --config $1 --scenes $2 --steps 3 --warmup 2 --linear-mode f16x3 > /dev/null 2>&1
   python tools/rocpd_timeline.py $(find /tmp/prof_$1 -name "*.db" | head -1) "k_preprocess<" $O/${TAG}_train_step_$1_b$2_f16x3.md --agg > /dev/null
 done
-B="--no-cpu-baseline --no-train-leg --no-infer-leg"
+B="--full --no-cpu-baseline --no-train-leg --no-infer-leg"
 { python bench.py --grid 128 $B | tail -1; python bench.py --ctx 2 $B | tail -1; python bench.py --ctx 4 $B | tail -1;
   python bench.py --ctx 4 --res 512 --sh-degree 4 --scenes 3 $B | tail -1; python bench.py --grid 512 --ctx 4 --res 512 --scenes 2 $B | tail -1;
   python tools/bench_train.py --config c3 --scenes 10 --steps 10 --warmup 3 --linear-mode f16x3 | tail -1;

@@ -4,12 +4,12 @@
 set -u
 OUT=${1:-gpurun_out/benchmarks}; mkdir -p "$OUT"
 run() { echo "== $*"; "$@" 2>&1 | tail -1 | tee -a "$OUT/all.jsonl" | cut -c1-260; }
-run python bench.py                                                              # headline M1 (+ roofline, CPU baseline)
-run python bench.py --grid 128 --no-cpu-baseline --no-train-leg --no-infer-leg                                 # 16 384 Gaussians / scene
-run python bench.py --ctx 2 --no-cpu-baseline --no-train-leg --no-infer-leg                                    # 131 072
-run python bench.py --ctx 4 --no-cpu-baseline --no-train-leg --no-infer-leg                                    # 262 144
-run python bench.py --ctx 4 --res 512 --sh-degree 4 --scenes 3 --no-cpu-baseline --no-train-leg --no-infer-leg # C5 stress shapes
-run python bench.py --grid 512 --ctx 4 --res 512 --scenes 2 --no-cpu-baseline --no-train-leg --no-infer-leg    # 1 048 576
+run python bench.py --full                                                              # headline M1 (+ roofline, CPU baseline)
+run python bench.py --full --grid 128 --no-cpu-baseline --no-train-leg --no-infer-leg                                 # 16 384 Gaussians / scene
+run python bench.py --full --ctx 2 --no-cpu-baseline --no-train-leg --no-infer-leg                                    # 131 072
+run python bench.py --full --ctx 4 --no-cpu-baseline --no-train-leg --no-infer-leg                                    # 262 144
+run python bench.py --full --ctx 4 --res 512 --sh-degree 4 --scenes 3 --no-cpu-baseline --no-train-leg --no-infer-leg # C5 stress shapes
+run python bench.py --full --grid 512 --ctx 4 --res 512 --scenes 2 --no-cpu-baseline --no-train-leg --no-infer-leg    # 1 048 576
 for MODE in f16x3 bf16x6 bf16x3; do       # M2, C3 (f16x3: the headline arithmetic; bf16x6: the library default; bf16x3: the reference's TF32 class)
   run python tools/bench_train.py --config c3 --scenes 10 --steps 10 --warmup 3 --linear-mode $MODE
 done
