@@ -13,11 +13,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 struct Adp {   // per-Gaussian intermediates shared by forward and backward
     float xyz[3], d, f;          // |xyz|, expm1(|xyz|)
     float p, op;                 // sigmoid(density), mapped opacity
@@ -219,9 +217,7 @@ int adapter_fwd(const VitAdapterArgs *a, float *means, float *cov, float *sh, fl
     const int64_t total = (int64_t)a->b * a->v * a->H * a->W;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_adapter_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *a, means, cov, sh, opac, scales, rot);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int adapter_bwd(const VitAdapterArgs *a, const float *d_means, const float *d_cov, const float *d_sh, const float *d_opac,
@@ -235,9 +231,7 @@ int adapter_bwd(const VitAdapterArgs *a, const float *d_means, const float *d_co
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_adapter_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, *a, d_means, d_cov, d_sh, d_opac,
                        d_pts0, d_ptsr, d_par0, d_parr, d_app);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 }  // namespace vit

@@ -21,27 +21,14 @@
 
 #include <atomic>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int HD = 64;          // head dim
 constexpr int QW = 32;          // queries per wavefront
 constexpr int QB = 128;         // queries per workgroup
 constexpr int KT = 64;          // keys per tile
 constexpr int KSTR = 65;        // LDS row stride of the K tile (floats)
-
-__device__ inline float wave_xor32(float x)
-{
-    // value of lane ^ 32 (the other half-wave of the same query)
-    float y = x;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    // after the swap: x = [x.lo, y.lo] , y = [x.hi, y.hi] with y == old x  ->  lanes<32 read y (= x.hi), lanes>=32 read x (= x.lo)
-    return (threadIdx.x & 32) ? x : y;
-}
 
 template <bool ROPE>
 __global__ void __launch_bounds__(256) k_attn_fwd(VitAttnArgs a, const float *__restrict__ q, const float *__restrict__ k,
@@ -262,8 +249,7 @@ int attention_fwd(const VitAttnArgs &a, const float *q, const float *k, const fl
         if (a.amax_out && !contiguous) return VIT_EINVAL;
         if (rope) hipLaunchKernelGGL(k_attn_fwd<true>, grid, dim3(256), 0, stream, b, q, k, v, out, lse);
         else hipLaunchKernelGGL(k_attn_fwd<false>, grid, dim3(256), 0, stream, b, q, k, v, out, lse);
-        e = hipGetLastError();
-        if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
+        if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (tail_rows) { const int rc = attention_fwd_tail(b, q, k, v, out, lse, tail_rows, stream); if (rc != VIT_OK) return rc; }
         return a.amax_out ? amax(out, (int64_t)a.B * a.Nq * a.H * HD, a.amax_out, stream) : VIT_OK;
     }

@@ -17,16 +17,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int HD = 64, TSTR = 65, TROWS = 32;
 constexpr float LOG2E = 1.4426950408889634f;
-
-__device__ inline int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
 
 // ------------------------------------------------------------------ delta
 __global__ void __launch_bounds__(256) k_attn_delta(const float *__restrict__ o, const float *__restrict__ g, float *__restrict__ delta,
@@ -100,23 +95,6 @@ __device__ inline void load_frag(float *f, const float *__restrict__ rp, int hal
             f[s] = uy * cy - vy * sy;      f[s + 8] = vy * cy + uy * sy;
             f[s + 16] = ux * cx - vx * sx; f[s + 24] = vx * cx + ux * sx;
         }
-    }
-}
-
-// inverse rotation of a transposed 64 x (lane) gradient held as two f32x16 (rows rowmap(r) and 32 + rowmap(r)):
-// features d < 16 pair with d + 16 -> registers r < 8 pair with r + 8 of the same accumulator.
-__device__ inline void unrotate(f32x16 &lo, f32x16 &hi, int half, int64_t py, int64_t px, const float *__restrict__ cos_tab,
-                                const float *__restrict__ sin_tab)
-{
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int d = rowmap(r, half);   // 0..15
-        const float cy = cos_tab[py * 16 + d], sy = sin_tab[py * 16 + d];
-        const float cx = cos_tab[px * 16 + d], sx = sin_tab[px * 16 + d];
-        const float gu = lo[r], gv = lo[r + 8];
-        lo[r] = gu * cy + gv * sy; lo[r + 8] = gv * cy - gu * sy;      // transpose of [[c,-s],[s,c]]
-        const float hu = hi[r], hv = hi[r + 8];
-        hi[r] = hu * cx + hv * sx; hi[r + 8] = hv * cx - hu * sx;
     }
 }
 
@@ -326,8 +304,7 @@ int attention_bwd(const VitAttnArgs &a, const float *q, const float *k, const fl
             hipLaunchKernelGGL(k_attn_bwd_kv<false>, gkv, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dk, dv);
             hipLaunchKernelGGL(k_attn_bwd_q<false>, gq, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dq);
         }
-        e = hipGetLastError();
-        if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
+        if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (q_tail || k_tail) { const int rc = attention_bwd_tails(b, q, k, v, lse, dout, delta_ws, dq, dk, dv, q_tail, k_tail, stream); if (rc != VIT_OK) return rc; }
         if (!want) return VIT_OK;
         if (packed) return amax(dq, (int64_t)a.B * a.Nq * 3 * hd, a.amax_dq, stream);

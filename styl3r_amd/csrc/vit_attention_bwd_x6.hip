@@ -1,7 +1,7 @@
 // vit_attention_bwd_x6.hip -- flash attention backward at fp32 accuracy on the bf16 matrix cores (head_dim 64, no mask).
 //
 // The same two passes as vit_attention_bwd.hip (k_attn_delta is shared), with every contraction in bf16x6 split arithmetic
-// (six v_mfma_f32_32x32x16_bf16 per 16-wide step; vit_gemm_x6.hip has the arithmetic, vit_attention_x6.hip the forward):
+// (six v_mfma_f32_32x32x16_bf16 per 16-wide step; vit_gemm_x6.hip explains the arithmetic, vit_common.h has the functions, vit_attention_x6.hip the forward):
 //   k_attn_bwd_q_x6    a wavefront owns 32 QUERIES (query = MFMA column = lane) and walks 32-key tiles:
 //                        S^T  = K Q^T        A = K rows  (LDS)   B = Q  pieces (regs)
 //                        dP^T = V dO^T       A = V rows  (LDS)   B = dO pieces (regs)
@@ -21,86 +21,23 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
-#include "vit_amax.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 namespace abx6 {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int HD = 64, TR = 32;                 // head dim, rows per tile
 constexpr int ROWB = 400, TROWB = 80;           // bytes per row of the two image kinds
 constexpr int ROWS_BYTES = TR * ROWB, T_BYTES = 3 * HD * TROWB;
 constexpr float LOG2E = 1.4426950408889634f;
 
-__device__ inline int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-
-__device__ inline void split2(float a, float b, uint32_t &p0, uint32_t &p1, uint32_t &p2)
-{
-    f32x2 f = {a, b};
-    const bf16x2 h0 = __builtin_convertvector(f, bf16x2);
-    const f32x2 r1 = f - __builtin_convertvector(h0, f32x2);
-    const bf16x2 h1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(h1, f32x2);
-    const bf16x2 h2 = __builtin_convertvector(r2, bf16x2);
-    p0 = __builtin_bit_cast(uint32_t, h0); p1 = __builtin_bit_cast(uint32_t, h1); p2 = __builtin_bit_cast(uint32_t, h2);
-}
-__device__ inline void split8(const float *v, bf16x8 (&f)[3])
-{
-    uint4 q0, q1, q2;
-    split2(v[0], v[1], q0.x, q1.x, q2.x);
-    split2(v[2], v[3], q0.y, q1.y, q2.y);
-    split2(v[4], v[5], q0.z, q1.z, q2.z);
-    split2(v[6], v[7], q0.w, q1.w, q2.w);
-    f[0] = __builtin_bit_cast(bf16x8, q0); f[1] = __builtin_bit_cast(bf16x8, q1); f[2] = __builtin_bit_cast(bf16x8, q2);
-}
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// NP == 2 ("f16x3", vit_attention_set_arith(3), round 6): eight ALREADY SCALED values -> two fp16x8 pieces (held in bf16x8 registers)
-__device__ inline void split8h(const float *v, bf16x8 (&f)[3])
-{
-    uint4 q0, q1;
-    f16_split2(v[0], v[1], q0.x, q1.x);
-    f16_split2(v[2], v[3], q0.y, q1.y);
-    f16_split2(v[4], v[5], q0.z, q1.z);
-    f16_split2(v[6], v[7], q0.w, q1.w);
-    f[0] = __builtin_bit_cast(bf16x8, q0); f[1] = __builtin_bit_cast(bf16x8, q1);
-}
-template <int NP> __device__ inline void split8p(const float *v, bf16x8 (&f)[3]) { if (NP == 2) split8h(v, f); else split8(v, f); }
 template <int NP> __device__ inline void split2p(float a, float b, uint32_t &p0, uint32_t &p1, uint32_t &p2)
 {
     if (NP == 2) f16_split2(a, b, p0, p1); else split2(a, b, p0, p1, p2);
 }
-// NP = 6: six partial products, smallest first; NP = 3 ("bf16x3", vit_attention_set_arith(2)): the three 2^-16-level products are left
-// out -- the third bf16 piece of every operand is then never used: the compiler drops its computation, the image stores skip it;
-// NP = 2 ("f16x3"): two fp16 pieces of value x power-of-two scale, h l' + l h' + h h' on the f16 MFMA (2^-22 per product).  Scales: Q, K, V, dO
+// NP = 6 / 3 ("bf16x3", vit_attention_set_arith(2)) / 2 ("f16x3", vit_attention_set_arith(3)): the products of mfma6 (vit_common.h).  Scales: Q, K, V, dO
 // from their tensors' |max| words (folded into `mul` of the loaders / stagers below), P the constant 2^14, dS a PER-LANE RUNNING scale (the
 // lane is the MFMA column = the query / key that owns the accumulators, so a lane's scale multiplies its whole accumulator column: when a
 // tile's dS outgrows the lane's current scale the column is rescaled by an exact power of two, as the online softmax rescales O).
-template <int NP>
-__device__ inline f32x16 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c)
-{
-    if (NP == 2) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[1]), __builtin_bit_cast(f16x8, b[0]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[1]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[0]), c, 0, 0, 0);
-        return c;
-    }
-    if (NP == 6) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    }
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
-}
-
 // ---- register fragments of one row (the MFMA B operand): step t covers d = 16 t + 8 half + j; rotated if ROPE, times `mul` ----
 template <bool ROPE, int NP>
 __device__ inline void load_row_pieces(bf16x8 (&f)[4][3], const float *__restrict__ rp, int half, const int64_t *__restrict__ pos2,
@@ -128,7 +65,7 @@ __device__ inline void load_row_pieces(bf16x8 (&f)[4][3], const float *__restric
     for (int t = 0; t < 4; ++t) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) x[t][j] *= mul;
-        split8p<NP>(x[t], f[t]);
+        split8p<NP>(x[t], f[t][0], f[t][1], f[t][2]);
     }
 }
 
@@ -173,10 +110,10 @@ __device__ inline void store_row_item(unsigned char *__restrict__ img, const Row
     }
     bf16x8 f[3];
     bf16x8 *dst = reinterpret_cast<bf16x8 *>(img + row * ROWB);
-    split8p<NP>(u, f);
+    split8p<NP>(u, f[0], f[1], f[2]);
     dst[sg * 3 + 0] = f[0]; dst[sg * 3 + 1] = f[1];
     if (NP == 6) dst[sg * 3 + 2] = f[2];
-    split8p<NP>(w, f);
+    split8p<NP>(w, f[0], f[1], f[2]);
     dst[(sg + 2) * 3 + 0] = f[0]; dst[(sg + 2) * 3 + 1] = f[1];
     if (NP == 6) dst[(sg + 2) * 3 + 2] = f[2];
 }
@@ -255,7 +192,7 @@ __device__ inline void t_times_regs(const unsigned char *__restrict__ img, int c
 #pragma unroll
         for (int j = 0; j < 8; ++j) xv[j] = NP == 2 ? x[8 * u + j] * xmul : x[8 * u + j];
         bf16x8 xf[3], tf[3];
-        split8p<NP>(xv, xf);
+        split8p<NP>(xv, xf[0], xf[1], xf[2]);
 #pragma unroll
         for (int p = 0; p < 3; ++p) tf[p] = *reinterpret_cast<const bf16x8 *>(ta + u * 32 + p * HD * TROWB);
         lo = mfma6<NP>(tf, xf, lo);
@@ -285,21 +222,6 @@ __device__ inline float ds_running_scale(const f32x16 &ds, float &s_run, f32x16 
     return s_run;
 }
 
-// inverse rotation of a transposed 64 x (lane) gradient held as two f32x16 (rows rowmap(r) and 32 + rowmap(r))
-__device__ inline void unrotate(f32x16 &lo, f32x16 &hi, int half, int64_t py, int64_t px, const float *__restrict__ cos_tab,
-                                const float *__restrict__ sin_tab)
-{
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int d = rowmap(r, half);   // 0..15
-        const float cy = cos_tab[py * 16 + d], sy = sin_tab[py * 16 + d];
-        const float cx = cos_tab[px * 16 + d], sx = sin_tab[px * 16 + d];
-        const float gu = lo[r], gv = lo[r + 8];
-        lo[r] = gu * cy + gv * sy; lo[r + 8] = gv * cy - gu * sy;      // transpose of [[c,-s],[s,c]]
-        const float hu = hi[r], hv = hi[r + 8];
-        hi[r] = hu * cx + hv * sx; hi[r + 8] = hv * cx - hu * sx;
-    }
-}
 __device__ inline uint32_t max_abs_32(const f32x16 &lo, const f32x16 &hi)
 {
     uint32_t m = 0;
@@ -381,7 +303,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_q_x6(VitAttnArgs a, const f
         const float sds = NP == 2 ? ds_running_scale(dp, s_run, dq0, dq1) : 1.f;
         t_times_regs<NP>(s_kt, col, half, dp, dq0, dq1, sds);
     }
-    mfma_result_fence();    // (loop exit right behind the last MFMAs: vit_amax.h)
+    mfma_result_fence();    // (loop exit right behind the last MFMAs: vit_common.h)
     if (NP == 2) {          // accumulated under (the lane's final dS scale) x (K's scale)
         const float f = 1.f / (s_run * sk);
 #pragma unroll

@@ -11,12 +11,9 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
-#include "vit_amax.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 namespace tail {
 constexpr int HD = 64, MAXN = 8192;      // rows of the OTHER operand that fit the score buffer
 
@@ -252,9 +249,7 @@ int attention_fwd_tail(const VitAttnArgs &a, const float *q, const float *k, con
     const dim3 grid(rows, a.H, a.B);
     if (a.cos_tab) hipLaunchKernelGGL(tail::k_attn_fwd_tail<true>, grid, dim3(64), 0, stream, a, q, k, v, out, lse, a.Nq - rows);
     else hipLaunchKernelGGL(tail::k_attn_fwd_tail<false>, grid, dim3(64), 0, stream, a, q, k, v, out, lse, a.Nq - rows);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 int attention_bwd_tails(const VitAttnArgs &a, const float *q, const float *k, const float *v, const float *lse, const float *dout,
                         const float *delta, float *dq, float *dk, float *dv, int q_rows, int k_rows, hipStream_t stream)
@@ -270,8 +265,6 @@ int attention_bwd_tails(const VitAttnArgs &a, const float *q, const float *k, co
         if (rope) hipLaunchKernelGGL(tail::k_attn_bwd_kv_tail<true>, g, dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dk, dv, a.Nk - k_rows);
         else hipLaunchKernelGGL(tail::k_attn_bwd_kv_tail<false>, g, dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dk, dv, a.Nk - k_rows);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

@@ -1,7 +1,7 @@
 // vit_attention_x6.hip -- flash attention forward at fp32 accuracy on the bf16 matrix cores (head_dim 64, no mask).
 //
 // vit_attention.hip runs both contractions on the exact-f32 MFMA (157 TF peak, 64 cycles per 32x32x2 step).  Here Q, K, V
-// and the probabilities are split into three bf16 pieces (vit_gemm_x6.hip has the arithmetic) and every contraction
+// and the probabilities are split into three bf16 pieces (vit_gemm_x6.hip explains the arithmetic, vit_common.h has the functions) and every contraction
 // takes six v_mfma_f32_32x32x16_bf16 per 16-wide step: 24 MFMAs x 32 cycles instead of 32 x 64 per (32 x 32 x 64) block,
 // 2.7x less matrix-pipe time, and the pipes that are busy are the bf16 ones the power budget is kinder to.
 //
@@ -20,89 +20,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
-#include "vit_amax.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 namespace ax6 {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int HD = 64, QW = 32, QB = 128, KT = 64;
 constexpr int KROW = 400;            // bytes per key row of the K image
 constexpr int VROW = 144;            // bytes per d row of one V^T piece plane
 constexpr int K_BYTES = KT * KROW, V_BYTES = 3 * HD * VROW;
 
-__device__ inline void split2(float a, float b, uint32_t &p0, uint32_t &p1, uint32_t &p2)
-{
-    f32x2 f = {a, b};
-    const bf16x2 h0 = __builtin_convertvector(f, bf16x2);
-    const f32x2 r1 = f - __builtin_convertvector(h0, f32x2);
-    const bf16x2 h1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(h1, f32x2);
-    const bf16x2 h2 = __builtin_convertvector(r2, bf16x2);
-    p0 = __builtin_bit_cast(uint32_t, h0); p1 = __builtin_bit_cast(uint32_t, h1); p2 = __builtin_bit_cast(uint32_t, h2);
-}
-// eight fp32 values -> three bf16x8 pieces
-__device__ inline void split8(const float *v, bf16x8 &f0, bf16x8 &f1, bf16x8 &f2)
-{
-    uint4 q0, q1, q2;
-    split2(v[0], v[1], q0.x, q1.x, q2.x);
-    split2(v[2], v[3], q0.y, q1.y, q2.y);
-    split2(v[4], v[5], q0.z, q1.z, q2.z);
-    split2(v[6], v[7], q0.w, q1.w, q2.w);
-    f0 = __builtin_bit_cast(bf16x8, q0); f1 = __builtin_bit_cast(bf16x8, q1); f2 = __builtin_bit_cast(bf16x8, q2);
-}
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-// NP == 2 ("f16x3"): eight ALREADY SCALED fp32 values -> two fp16x8 pieces (in bf16x8 registers: only the MFMA reinterprets them)
-__device__ inline void split8h(const float *v, bf16x8 &f0, bf16x8 &f1)
-{
-    uint4 q0, q1;
-    f16_split2(v[0], v[1], q0.x, q1.x);
-    f16_split2(v[2], v[3], q0.y, q1.y);
-    f16_split2(v[4], v[5], q0.z, q1.z);
-    f16_split2(v[6], v[7], q0.w, q1.w);
-    f0 = __builtin_bit_cast(bf16x8, q0); f1 = __builtin_bit_cast(bf16x8, q1);
-}
-template <int NP> __device__ inline void split8p(const float *v, bf16x8 &f0, bf16x8 &f1, bf16x8 &f2)
-{
-    if (NP == 2) split8h(v, f0, f1); else split8(v, f0, f1, f2);
-}
-__device__ inline float wave_xor32(float x)
-{
-    float y = x;
-    asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(x), "+v"(y));
-    return (threadIdx.x & 32) ? x : y;
-}
-
-// NP = 6: six partial products, smallest first; NP = 3 ("bf16x3"): without the three 2^-16-level products (see vit_attention_bwd_x6.hip);
-// NP = 2 ("f16x3", round 6): two fp16 pieces per operand, h l' + l h' + h h' on v_mfma_f32_32x32x16_f16 -- 2^-22 per product at the MFMA
-// count of bf16x3.  Operands carry power-of-two scales: Q, K, V from their tensors' |max| words (VitAttnArgs.amax_q / _k / _v), the
-// probabilities the constant 2^14 (p <= 1); the scores are un-scaled before the softmax, the output in the epilogue.
-template <int NP>
-__device__ inline f32x16 mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16 c)
-{
-    if (NP == 2) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[1]), __builtin_bit_cast(f16x8, b[0]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[1]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a[0]), __builtin_bit_cast(f16x8, b[0]), c, 0, 0, 0);
-        return c;
-    }
-    if (NP == 6) {
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    }
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-    return c;
-}
-
+// NP = 6 / 3 / 2: the products of mfma6 (vit_common.h).  In f16x3 (round 6) the operands carry power-of-two scales: Q, K, V from their tensors'
+// |max| words (VitAttnArgs.amax_q / _k / _v), the probabilities the constant 2^14 (p <= 1); the scores are un-scaled before the softmax, the
+// output in the epilogue.
 template <bool ROPE, int NP>
 __global__ void __launch_bounds__(256, 2) k_attn_fwd_x6(VitAttnArgs a, const float *__restrict__ q, const float *__restrict__ k,
                                                         const float *__restrict__ v, float *__restrict__ out, float *__restrict__ lse)
@@ -260,7 +189,7 @@ __global__ void __launch_bounds__(256, 2) k_attn_fwd_x6(VitAttnArgs a, const flo
                 }
             }
         }
-        mfma_result_fence();            // (the branch around the second block's MFMAs joins here: see vit_amax.h)
+        mfma_result_fence();            // (the branch around the second block's MFMAs joins here: see vit_common.h)
         if (NP == 2) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) { st0[r] *= inv_qk; st1[r] *= inv_qk; }

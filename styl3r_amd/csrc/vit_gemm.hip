@@ -13,15 +13,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int BM = 128, BK = 16, LDT = 132;   // LDT: padded row length of the k-major tiles (BN = 64 * TN)
-
-__device__ inline float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 
 // TN = 32-column MFMA tiles per wavefront along N: TN = 2 -> 128x128 workgroup tile, TN = 1 -> 128x64 (more, smaller
 // tiles for N <= 1024 layers, whose 128x128 tiling leaves most CUs with one tile while a few carry two)
@@ -147,8 +142,6 @@ int linear_fwd(const float *x, const float *w, const float *bias, const float *r
     if (act == 1) { if (narrow) VIT_LAUNCH_LINEAR(1, 1); else VIT_LAUNCH_LINEAR(1, 2); }
     else { if (narrow) VIT_LAUNCH_LINEAR(0, 1); else VIT_LAUNCH_LINEAR(0, 2); }
 #undef VIT_LAUNCH_LINEAR
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

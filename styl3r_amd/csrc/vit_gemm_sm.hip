@@ -2,7 +2,7 @@
 // for NARROW outputs (N <= 768: the decoders' proj / projq / projk / projv / fc2 and the input-gradient GEMMs of their qkv / fc1 in the train step).
 // Reached through vit_linear_x6r_fwd with cfg = 5 (one problem) and vit_linear_sm_grouped (two problems of one shape: the dual decoders).
 //
-//     out (M,N) = [residual +] act( x (M,K) . w^T (N,K) + bias )            same operands, split functions and epilogue as vit_gemm_x6.hip; BLOCK weight image
+//     out (M,N) = [residual +] act( x (M,K) . w^T (N,K) + bias )            same operands, split functions (vit_common.h) and epilogue as vit_gemm_x6.hip; BLOCK weight image
 //
 // What is different from k_linear_x6 (128-row tiles, LDS-staged operands, a barrier pair per 16-deep slab, split-K through fp32 atomics into a
 // zero-filled output when the tiles cannot fill the chip -- at M = 257 / 514 that is a zero-fill launch, 640 workgroups of 8 slabs each, 128-row
@@ -24,45 +24,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
-#include "vit_amax.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
 int x6_products();
 void x6_take_amax(const uint32_t *&a, const uint32_t *&b);
 uint32_t *x6_take_output_amax();
 
 namespace sm {
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ inline float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__device__ inline float gelu_grad_exact(float x)
-{
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
-// two fp32 values -> their three bf16 pieces (the functions of vit_gemm_x6.hip: a tensor split here and there gets the same pieces)
-__device__ inline void split2_bf16(float a, float b, uint32_t &p0, uint32_t &p1, uint32_t &p2)
-{
-    f32x2 f = {a, b};
-    const bf16x2 h0 = __builtin_convertvector(f, bf16x2);
-    const f32x2 r1 = f - __builtin_convertvector(h0, f32x2);
-    const bf16x2 h1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(h1, f32x2);
-    const bf16x2 h2 = __builtin_convertvector(r2, bf16x2);
-    p0 = __builtin_bit_cast(uint32_t, h0); p1 = __builtin_bit_cast(uint32_t, h1); p2 = __builtin_bit_cast(uint32_t, h2);
-}
-template <int NPROD> __device__ inline f32x16 mma(const uint4 &a, const uint4 &b, const f32x16 &c)
-{
-    if (NPROD == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-
 constexpr int LPAD = 4;          // floats of padding behind a column of the partial tile in LDS (column stride 32 TM + 4: b128 accesses of 8 lanes hit 32 banks)
 
 // compiler fence: memory accesses (global loads, LDS traffic) stay on their side.  The MFMAs of a stage read their A pieces from LDS, so they are
@@ -149,8 +118,8 @@ __global__ void __launch_bounds__(NW * 64) k_linear_sm(const SmArgs args)
                 f16_split2(v.x * sx, v.y * sx, p0[0], p1[0]);
                 f16_split2(v.z * sx, v.w * sx, p0[1], p1[1]);
             } else {
-                split2_bf16(v.x, v.y, p0[0], p1[0], p2[0]);
-                split2_bf16(v.z, v.w, p0[1], p1[1], p2[1]);
+                split2(v.x, v.y, p0[0], p1[0], p2[0]);
+                split2(v.z, v.w, p0[1], p1[1], p2[1]);
             }
             const int slot2 = a_slot(row, seg >> 1) * 2 + (seg & 1);          // in uint2 units
             base[slot2] = make_uint2(p0[0], p0[1]);
@@ -365,9 +334,7 @@ static int launch_sm(const sm::SmArgs &a, int groups, hipStream_t stream)
     else VIT_SM_NP(2, 4);
 #undef VIT_SM_NP
 #undef VIT_SM_LAUNCH
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 static const uint32_t *block_image_amax(const void *wpb, int N, int K)

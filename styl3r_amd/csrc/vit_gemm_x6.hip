@@ -19,24 +19,16 @@
 // 128 x (64 TN) output tile per workgroup, 4 wavefronts (2x2) of 64 x 32TN sub-tiles, v_mfma_f32_32x32x16_bf16,
 // K consumed 16 at a time through double-buffered, XOR-swizzled 96-byte LDS rows; two register stages keep the global
 // loads of slab k+2 in flight while slab k feeds the MFMAs; three workgroups per CU.
+// The split functions, the "f16x3" mode (two fp16 pieces, NPROD == 2) and its |max| words are in vit_common.h.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <atomic>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace x6 {
 constexpr int BM = 128, BK = 16, ROWQ = 6;   // LDS row = 6 x 16-B slots (2 k-groups x 3 pieces), no padding
 // slot s of row r lives at physical slot s ^ ((r >> 3) & 1): with 96-byte rows the 16 lanes of every ds_read_b128 lane
@@ -48,25 +40,6 @@ __device__ inline int swz(int row, int slot) { return slot ^ ((row >> 3) & 1); }
 // conflict on every store (r03 PMC: a third of the LDS cycles of k_wgrad_x6).  Flipping the slot pair on row bit 2 as well separates rows
 // r and r + 4; the ds_read_b128 lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}) still pair rows whose flags differ.
 __device__ inline int swz_t(int row, int slot) { return slot ^ (((row >> 3) ^ (row >> 2)) & 1); }
-
-// Workgroup id -> output tile.  (1) Consecutive workgroup ids are dealt round-robin to the 8 XCDs, each with its own
-// L2: XCD x gets one CONTIGUOUS range of the tile sequence (exact partition for any tile count).  (2) The sequence
-// itself walks the tile grid in groups of GM row-tiles, column by column, so the ~64 tiles an XCD has in flight form
-// an ~8x8 block: every A row-panel and every B column-panel fetched into that L2 is reused ~8 times instead of the
-// 24x / 2.7x of a row-major walk (the B panels do not fit the 4 MB L2 and were re-streamed over the fabric).
-__device__ inline void tile_of_block(int bid, int tiles_m, int tiles_n, int &tm, int &tn)
-{
-    constexpr int GM = 8;
-    const int ntiles = tiles_m * tiles_n, q = ntiles >> 3, r = ntiles & 7;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int pid = xcd * q + min(xcd, r) + local;
-    const int per_group = GM * tiles_n;
-    const int group = pid / per_group, first_m = group * GM;
-    const int gsz = min(tiles_m - first_m, GM);
-    const int in_group = pid - group * per_group;
-    tm = first_m + in_group % gsz;
-    tn = in_group / gsz;
-}
 
 // Zero fill of a split-contraction output.  (Not hipMemsetAsync: its graph node is not replayed faithfully by this runtime -- captured
 // into a hipGraph, the second and later replays leave half of the words untouched -- so the serving graphs of styl3r_amd/graphs.py
@@ -85,103 +58,8 @@ __global__ void __launch_bounds__(256) k_zero_words(uint32_t *__restrict__ p, si
     }
 }
 
-__device__ inline float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-// d/dx of the exact GELU: Phi(x) + x phi(x)   (aten's GeluBackward, approximate = "none")
-__device__ inline float gelu_grad_exact(float x)
-{
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
-// two fp32 values -> their three bf16 pieces, each packed (lo = first value)
-__device__ inline void split2(float a, float b, uint32_t &p0, uint32_t &p1, uint32_t &p2)
-{
-    f32x2 f = {a, b};
-    const bf16x2 h0 = __builtin_convertvector(f, bf16x2);
-    const f32x2 r1 = f - __builtin_convertvector(h0, f32x2);
-    const bf16x2 h1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(h1, f32x2);
-    const bf16x2 h2 = __builtin_convertvector(r2, bf16x2);
-    p0 = __builtin_bit_cast(uint32_t, h0); p1 = __builtin_bit_cast(uint32_t, h1); p2 = __builtin_bit_cast(uint32_t, h2);
-}
-
-__device__ inline void split8(const float4 &lo, const float4 &hi, uint4 &q0, uint4 &q1, uint4 &q2)
-{
-    split2(lo.x, lo.y, q0.x, q1.x, q2.x);
-    split2(lo.z, lo.w, q0.y, q1.y, q2.y);
-    split2(hi.x, hi.y, q0.z, q1.z, q2.z);
-    split2(hi.z, hi.w, q0.w, q1.w, q2.w);
-}
-
-// ---- "f16x3" (NPROD == 2): two fp16 pieces per fp32 value, three products on v_mfma_f32_32x32x16_f16 -------------------------------
-// An fp32 value scaled by a power of two splits into two fp16 pieces, a s = h + l + O(2^-22 |a s|) (h = round-to-nearest fp16, 11-bit
-// significand; l = fp16 of the exact residual), and h h' + (h l' + l h') reproduces the product to 2^-22 -- 64 x tighter than the three
-// bf16 products of "bf16x3" (2^-16) at the SAME three MFMAs per k-step and the same two-piece data path.  What fp16 lacks is range
-// (2^-24 .. 65 504), so every operand TENSOR carries a power-of-two scale taken from its own absolute maximum (`k_amax`, an exact integer
-// max over the fp32 bit patterns): 2^14 <= amax s < 2^15.  Elements down to 2^-17 amax keep all 22 bits, smaller ones an absolute error of
-// 2^-39 amax -- below the fp32 rounding of any sum they enter.  Scales are powers of two, so scaling and un-scaling are exact; the epilogue
-// multiplies the fp32 accumulator by the two inverse scales.
-// An "|max| word" is 64 words, ONE PER 128-BYTE CACHE LINE (8 KiB in all): producers fold their maxima into word (workgroup id + wave) & 63.
-// L2 atomics serialise per cache line at ~10 ns each -- thousands of waves folding into one line cost 20 - 50 us per launch (measured: +9 ms per
-// train step from the LayerNorm epilogues alone, and no better with 64 words packed into two lines); spread over 64 lines they run in parallel
-// channels.  Readers take the max over the 64 words with one gather load and a wave reduction.
-constexpr int AMAX_STRIDE = 32;        // words between the 64 slots
-__device__ inline uint32_t amax_line(const uint32_t *__restrict__ line)
-{
-    uint32_t m = line[(threadIdx.x & 63) * AMAX_STRIDE];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    return m;
-}
-__device__ inline void amax_fold(uint32_t *__restrict__ line, uint32_t m)     // m: this lane's maximum; one guarded atomic per wave
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    uint32_t *w = line + ((blockIdx.x + 7u * blockIdx.y + (threadIdx.x >> 6)) & 63u) * AMAX_STRIDE;
-    if ((threadIdx.x & 63) == 0 && m > __atomic_load_n(w, __ATOMIC_RELAXED)) atomicMax(w, m);
-}
-__device__ inline float f16_scale(uint32_t amax_bits)
-{
-    const int e = (int)((amax_bits >> 23) & 0xff);
-    if (e == 0 || e == 255) return 1.f;        // all-zero / denormal tensor; Inf / NaN inside (those propagate on their own)
-    const int se = min(max(127 + 14 - (e - 127), 27), 227);       // s in [2^-100, 2^100]
-    return __builtin_bit_cast(float, (uint32_t)se << 23);
-}
-
-// two (scaled) fp32 values -> their two fp16 pieces, each packed (lo = first value)
-__device__ inline void split2h(float a, float b, uint32_t &p0, uint32_t &p1)
-{
-    // h = RNE fp16 of the pair; l = fp16 of the exact residuals a - h (v_fma_mix_f32 reads the fp16 halves in place: no v_cvt_f32_f16)
-    float ra, rb;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p0) : "v"(a), "v"(b));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "v"(p0));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "v"(p0));
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p1) : "v"(ra), "v"(rb));
-}
-
-// NPROD == 6 / 3: three bf16 pieces (the third unused by 3); NPROD == 2: two fp16 pieces of s * value (q2 is left alone)
-template <int NPROD> __device__ inline void split8s(const float4 &lo, const float4 &hi, float s, uint4 &q0, uint4 &q1, uint4 &q2)
-{
-#ifdef VIT_EXP_NOSPLIT   /* experiment builds only (tools/exp_nosplit.sh): the operand as if it arrived already split -- WRONG results, the same loads / LDS traffic / MFMAs */
-    if (NPROD == 2) { q0 = __builtin_bit_cast(uint4, lo); q1 = __builtin_bit_cast(uint4, hi); return; }
-#endif
-    if (NPROD == 2) {
-        split2h(lo.x * s, lo.y * s, q0.x, q1.x);
-        split2h(lo.z * s, lo.w * s, q0.y, q1.y);
-        split2h(hi.x * s, hi.y * s, q0.z, q1.z);
-        split2h(hi.z * s, hi.w * s, q0.w, q1.w);
-    } else {
-        split8(lo, hi, q0, q1, q2);
-    }
-}
-
-template <int NPROD> __device__ inline f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c)
-{
-    if (NPROD == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // absolute maximum of a tensor as the bit pattern of |x| (monotone for non-negative floats; a NaN wins, so it stays visible): one
-// guarded atomicMax per wave into a pre-zeroed 64-word line (amax_fold)
+// guarded atomicMax per wave into a pre-zeroed 64-word line (amax_word_fold)
 __global__ void __launch_bounds__(256) k_amax(const float *__restrict__ x, int64_t n, uint32_t *__restrict__ out)
 {
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -200,7 +78,7 @@ __global__ void __launch_bounds__(256) k_amax(const float *__restrict__ x, int64
     } else {
         for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) m = max(m, __builtin_bit_cast(uint32_t, x[i]) & 0x7fffffffu);
     }
-    amax_fold(out, m);
+    amax_word_fold(out, m, blockIdx.x + 7u * blockIdx.y);
 }
 
 // SPLITK: gridDim.y workgroups share one output tile, each contracting its own range of K slabs and adding its partial
@@ -217,7 +95,7 @@ __global__ void __launch_bounds__(256, 3) k_linear_x6(const float *__restrict__ 
     uint32_t omax = 0;          // |max| of the values this lane stores (published to *amax_out: the consumer's f16x3 scale without a pass of its own)
     // f16x3: scale of the activation tensor (applied while it is split) and the two inverse scales of the epilogue
     float sx = 1.f, ix = 1.f, iw = 1.f;
-    if (NPROD == 2) { sx = f16_scale(amax_line(amax_x)); ix = 1.f / sx; iw = 1.f / f16_scale(amax_line(amax_w)); }
+    if (NPROD == 2) { sx = f16_scale_of(amax_word_read(amax_x)); ix = 1.f / sx; iw = 1.f / f16_scale_of(amax_word_read(amax_w)); }
     // (the 64-row B tile is allocated at the 128-row size: keeps the narrow variant at three workgroups per CU; four
     // thrash the L2 on the N = 1024 layers: measured -5 %)
     __shared__ uint4 sA[2][BM * ROWQ], sB[2][128 * ROWQ];
@@ -373,7 +251,7 @@ __global__ void __launch_bounds__(256, 3) k_linear_x6(const float *__restrict__ 
         }
     }
     if (!SPLITK && amax_out) {   // (wave-uniform branch; one atomic per wave)
-        amax_fold(amax_out, omax);
+        amax_word_fold(amax_out, omax, blockIdx.x + 7u * blockIdx.y);
     }
 }
 
@@ -391,7 +269,7 @@ __global__ void __launch_bounds__(256, 2) k_wgrad_x6(const float *__restrict__ d
 {
     constexpr int TN = 2, BN = 128;
     float sa = 1.f, sb = 1.f, ia = 1.f, ib = 1.f;          // f16x3: tensor scales of dY and X, their inverses for the epilogue
-    if (NPROD == 2) { sa = f16_scale(amax_line(amax_dy)); sb = f16_scale(amax_line(amax_x)); ia = 1.f / sa; ib = 1.f / sb; }
+    if (NPROD == 2) { sa = f16_scale_of(amax_word_read(amax_dy)); sb = f16_scale_of(amax_word_read(amax_x)); ia = 1.f / sa; ib = 1.f / sb; }
     __shared__ uint4 sA[2][BM * ROWQ], sB[2][BN * ROWQ];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
@@ -566,7 +444,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_x6(const float *__restrict__ in
 {
     constexpr int TN = 2, BN = 128, TAPS = KS * KS;
     float sb = 1.f, ia = 1.f, ib = 1.f;                     // f16x3: activation scale (rides in the border mask), inverse scales
-    if (NPROD == 2) { sb = f16_scale(amax_line(amax_in)); ib = 1.f / sb; ia = 1.f / f16_scale(amax_line(amax_w)); }
+    if (NPROD == 2) { sb = f16_scale_of(amax_word_read(amax_in)); ib = 1.f / sb; ia = 1.f / f16_scale_of(amax_word_read(amax_w)); }
     __shared__ uint4 sA[2][BM * ROWQ], sB[2][BN * ROWQ];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
@@ -724,7 +602,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3h_x6(const float *__restrict__ 
     constexpr int TY = 4, TX = 32, HY = TY + 2, HX = TX + 2, HP = HY * HX;      // 204 halo pixels
     __shared__ uint4 sA[2][BM * ROWQ], sP[2][HP * ROWQ];                         // 24 KB + 38.25 KB
     float sb = 1.f, ia = 1.f, ib = 1.f;                     // f16x3: activation scale (rides in the border mask), inverse scales
-    if (NPROD == 2) { sb = f16_scale(amax_line(amax_in)); ib = 1.f / sb; ia = 1.f / f16_scale(amax_line(amax_w)); }
+    if (NPROD == 2) { sb = f16_scale_of(amax_word_read(amax_in)); ib = 1.f / sb; ia = 1.f / f16_scale_of(amax_word_read(amax_w)); }
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
     const int wm = wave >> 1, wn = wave & 1;
@@ -896,7 +774,7 @@ __global__ void __launch_bounds__(256, 2) k_conv3h_x6(const float *__restrict__ 
         }
     }
     if (amax_out && gridDim.y == 1) {
-        amax_fold(amax_out, omax);
+        amax_word_fold(amax_out, omax, blockIdx.x + 7u * blockIdx.y);
     }
 }
 
@@ -916,7 +794,7 @@ __global__ void __launch_bounds__(256, 2) k_conv_wgrad_x6(const float *__restric
 {
     constexpr int TN = 2, BN = 128, TAPS = KS * KS;
     float sa = 1.f, sb = 1.f, ia = 1.f, ib = 1.f;          // f16x3: tensor scales of dY and the input (the latter rides in the row mask)
-    if (NPROD == 2) { sa = f16_scale(amax_line(amax_dy)); sb = f16_scale(amax_line(amax_in)); ia = 1.f / sa; ib = 1.f / sb; }
+    if (NPROD == 2) { sa = f16_scale_of(amax_word_read(amax_dy)); sb = f16_scale_of(amax_word_read(amax_in)); ia = 1.f / sa; ib = 1.f / sb; }
     __shared__ uint4 sA[2][BM * ROWQ], sB[2][BN * ROWQ];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int half = lane >> 5, col = lane & 31;
@@ -1061,14 +939,14 @@ __global__ void __launch_bounds__(256, 2) k_conv_wgrad_x6(const float *__restric
 // w (R, C) row-major fp32 -> packed[r][c/8][piece][8] bf16.  transpose = 0: (r, c) = (row, col) of w, R x C = rows x cols.
 // transpose = 1: packs w^T, i.e. output row r = column r of w, output k index = row of w (tiled through LDS so both the
 // reads and the writes stay coalesced).
-// NPROD == 2 ("f16x3"): two fp16 pieces of w * f16_scale(amax_line(amax)) in slots 0 / 1 (slot 2 is never read in that mode)
+// NPROD == 2 ("f16x3"): two fp16 pieces of w * f16_scale_of(amax_word_read(amax)) in slots 0 / 1 (slot 2 is never read in that mode)
 template <int NPROD>
 __global__ void __launch_bounds__(256) k_split_rows(const float *__restrict__ w, uint4 *__restrict__ packed, int64_t groups,
                                                     const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail)
 {
     const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one 8-wide k group per thread
-    if (NPROD == 2 && blockIdx.x == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_STRIDE] = amax[threadIdx.x * AMAX_STRIDE];      // the line the kernels that read this image take their inverse scale from
-    const float sw = NPROD == 2 ? f16_scale(amax_line(amax)) : 1.f;     // (whole waves: before any lane leaves)
+    if (NPROD == 2 && blockIdx.x == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_WORD_STRIDE] = amax[threadIdx.x * AMAX_WORD_STRIDE];      // the line the kernels that read this image take their inverse scale from
+    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;     // (whole waves: before any lane leaves)
     if (g >= groups) return;
     const float4 lo = reinterpret_cast<const float4 *>(w)[g * 2], hi = reinterpret_cast<const float4 *>(w)[g * 2 + 1];
     uint4 q0, q1, q2 = make_uint4(0, 0, 0, 0);
@@ -1080,8 +958,8 @@ template <int NPROD>
 __global__ void __launch_bounds__(256) k_split_transposed(const float *__restrict__ w, uint4 *__restrict__ packed, int rows,
                                                           int cols, const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail)
 {
-    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_STRIDE] = amax[threadIdx.x * AMAX_STRIDE];
-    const float sw = NPROD == 2 ? f16_scale(amax_line(amax)) : 1.f;     // (whole waves: before any lane leaves)
+    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_WORD_STRIDE] = amax[threadIdx.x * AMAX_WORD_STRIDE];
+    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;     // (whole waves: before any lane leaves)
     // tile: 64 source rows (-> k of the output) x 32 source columns (-> output rows)
     __shared__ float s[64][33];
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 32;
@@ -1112,11 +990,11 @@ __global__ void __launch_bounds__(256) k_split_conv_pair(const float *__restrict
                                                          const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail_f, uint32_t *__restrict__ tail_dx)
 {
     if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
-        const uint32_t a = amax[threadIdx.x * AMAX_STRIDE];
-        tail_f[threadIdx.x * AMAX_STRIDE] = a;
-        if (pdx) tail_dx[threadIdx.x * AMAX_STRIDE] = a;
+        const uint32_t a = amax[threadIdx.x * AMAX_WORD_STRIDE];
+        tail_f[threadIdx.x * AMAX_WORD_STRIDE] = a;
+        if (pdx) tail_dx[threadIdx.x * AMAX_WORD_STRIDE] = a;
     }
-    const float sw = NPROD == 2 ? f16_scale(amax_line(amax)) : 1.f;
+    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;
     __shared__ float s[CW_T][CW_T * CW_TAPS_MAX + 1];            // [co][ci * kk + tap]
     const int co0 = blockIdx.y * CW_T, ci0 = blockIdx.x * CW_T, run = CW_T * kk;
     for (int i = threadIdx.x; i < CW_T * run; i += 256) {         // per co: CW_T * kk contiguous floats
@@ -1200,9 +1078,7 @@ int amax(const float *x, int64_t n, void *out, hipStream_t stream)     // *out m
     (void)hipGetLastError();
     const int64_t blocks = (n / 16 + 255) / 256;            // ~four 16-byte loads per lane; 2048 workgroups = 8 per CU at most
     hipLaunchKernelGGL(x6::k_amax, dim3((unsigned)(blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks))), dim3(256), 0, stream, x, n, static_cast<uint32_t *>(out));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 // number of contraction splits for the weight-gradient kernels (2 resident workgroups per CU): one full round of 512
@@ -1240,9 +1116,7 @@ int split_conv_weight_pair(const float *w, void *packed_fwd, void *packed_dx, in
         hipLaunchKernelGGL(x6::k_split_conv_pair<2>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_fwd), static_cast<uint4 *>(packed_dx), Co, Ci, kk, am, tf, td);
     } else
         hipLaunchKernelGGL(x6::k_split_conv_pair<6>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_fwd), static_cast<uint4 *>(packed_dx), Co, Ci, kk, am, tf, td);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int split_weight(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream)
@@ -1270,9 +1144,7 @@ int split_weight(const float *w, void *packed, int rows, int cols, int transpose
         if (f16) hipLaunchKernelGGL(x6::k_split_transposed<2>, dim3((cols + 31) / 32, (rows + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, am, tail);
         else hipLaunchKernelGGL(x6::k_split_transposed<6>, dim3((cols + 31) / 32, (rows + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, am, tail);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 static bool zero_fill(void *p, size_t bytes, hipStream_t stream)
@@ -1325,8 +1197,7 @@ int linear_x6_fwd(const float *x, const void *wp, const float *bias, const float
         else { if (narrow) VIT_LAUNCH_X6(0, 1); else VIT_LAUNCH_X6(0, 2); }
 #undef VIT_LAUNCH_X6
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
+    if (launch_status() != VIT_OK) return VIT_ELAUNCH;
     if (am_out && S > 1) return amax(out, (int64_t)M * N, am_out, stream);      // split-K partial sums: the |max| of the result needs its own pass
     return VIT_OK;
 }
@@ -1380,9 +1251,7 @@ int linear_x6_wgrad(const float *dy, const float *x, float *dw, float *dbias, in
     if (np == 3) hipLaunchKernelGGL(x6::k_wgrad_x6<3>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x);
     else if (np == 2) hipLaunchKernelGGL(x6::k_wgrad_x6<2>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x);
     else hipLaunchKernelGGL(x6::k_wgrad_x6<6>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float *residual, float *out, int B, int Ci, int Co,
                 int H, int W, int ksize, int flags, hipStream_t stream)
@@ -1418,8 +1287,7 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
     } while (0)
         if (relu_in) VIT_LAUNCH_H6(true); else VIT_LAUNCH_H6(false);
 #undef VIT_LAUNCH_H6
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
+        if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (am_out && S > 1) return amax(out, NP * Co, am_out, stream);      // partial sums: the |max| of the result needs its own pass
         return VIT_OK;
     }
@@ -1437,8 +1305,7 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
     if (ksize == 3) { if (relu_in) VIT_LAUNCH_C6(3, true); else VIT_LAUNCH_C6(3, false); }
     else { if (relu_in) VIT_LAUNCH_C6(1, true); else VIT_LAUNCH_C6(1, false); }
 #undef VIT_LAUNCH_C6
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
+    if (launch_status() != VIT_OK) return VIT_ELAUNCH;
     if (am_out) return amax(out, NP * Co, am_out, stream);      // (k_conv_x6 does not publish its output's |max| itself: one pass here)
     return VIT_OK;
 }
@@ -1467,8 +1334,6 @@ int conv_x6_wgrad(const float *dy, const float *in, float *dw, float *dbias, int
     if (ksize == 3) { if (relu_in) VIT_LAUNCH_G6(3, true); else VIT_LAUNCH_G6(3, false); }
     else { if (relu_in) VIT_LAUNCH_G6(1, true); else VIT_LAUNCH_G6(1, false); }
 #undef VIT_LAUNCH_G6
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

@@ -1,4 +1,4 @@
-// vit_gemm_x6r.hip -- the bf16x6 Linear (see vit_gemm_x6.hip for the arithmetic) with an LDS-DMA operand ring.
+// vit_gemm_x6r.hip -- the bf16x6 Linear (see vit_gemm_x6.hip for the arithmetic, vit_common.h for the split functions) with an LDS-DMA operand ring.
 //
 //     out (M,N) = [residual +] act( x (M,K) . w^T (N,K) + bias )
 //
@@ -35,128 +35,17 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
 int x6_products();     // vit_gemm_x6.hip: partial products per launch (6 / 3; 2 = "f16x3"), per host thread
 void x6_take_amax(const uint32_t *&a, const uint32_t *&b);      // vit_gemm_x6.hip: the announced |max| words of the next launch (consumed)
 uint32_t *x6_take_output_amax();                                 // vit_gemm_x6.hip: where the next launch publishes the |max| of its output (or null)
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 namespace x6r {
 constexpr int BK = 16;
 
-__device__ inline float gelu_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
-__device__ inline float gelu_grad_exact(float x)     // as in vit_gemm_x6.hip (act = 2: the input-gradient GEMM of the layer behind a GELU)
-{
-    return 0.5f * (1.0f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
-__device__ inline void split2(float a, float b, uint32_t &p0, uint32_t &p1, uint32_t &p2)
-{
-    f32x2 f = {a, b};
-    const bf16x2 h0 = __builtin_convertvector(f, bf16x2);
-    const f32x2 r1 = f - __builtin_convertvector(h0, f32x2);
-    const bf16x2 h1 = __builtin_convertvector(r1, bf16x2);
-    const f32x2 r2 = r1 - __builtin_convertvector(h1, f32x2);
-    const bf16x2 h2 = __builtin_convertvector(r2, bf16x2);
-    p0 = __builtin_bit_cast(uint32_t, h0); p1 = __builtin_bit_cast(uint32_t, h1); p2 = __builtin_bit_cast(uint32_t, h2);
-}
-
-template <typename V4> __device__ inline void split8(const V4 &lo, const V4 &hi, bf16x8 &f0, bf16x8 &f1, bf16x8 &f2)
-{
-    uint4 q0, q1, q2;
-    split2(lo.x, lo.y, q0.x, q1.x, q2.x);
-    split2(lo.z, lo.w, q0.y, q1.y, q2.y);
-    split2(hi.x, hi.y, q0.z, q1.z, q2.z);
-    split2(hi.z, hi.w, q0.w, q1.w, q2.w);
-    f0 = __builtin_bit_cast(bf16x8, q0); f1 = __builtin_bit_cast(bf16x8, q1); f2 = __builtin_bit_cast(bf16x8, q2);
-}
-
-// ---- "f16x3" (NPROD == 2; see vit_gemm_x6.hip): two fp16 pieces of value * 2^k, k from the operand tensor's |max| ---------------
-// An "|max| word" is 64 words, ONE PER 128-BYTE CACHE LINE (8 KiB in all): producers fold their maxima into word (workgroup id + wave) & 63.
-// L2 atomics serialise per cache line at ~10 ns each -- thousands of waves folding into one line cost 20 - 50 us per launch (measured: +9 ms per
-// train step from the LayerNorm epilogues alone, and no better with 64 words packed into two lines); spread over 64 lines they run in parallel
-// channels.  Readers take the max over the 64 words with one gather load and a wave reduction.
-constexpr int AMAX_STRIDE = 32;        // words between the 64 slots
-__device__ inline uint32_t amax_line(const uint32_t *__restrict__ line)
-{
-    uint32_t m = line[(threadIdx.x & 63) * AMAX_STRIDE];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    return m;
-}
-__device__ inline void amax_fold(uint32_t *__restrict__ line, uint32_t m)     // m: this lane's maximum; one guarded atomic per wave
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    uint32_t *w = line + ((blockIdx.x + 7u * blockIdx.y + (threadIdx.x >> 6)) & 63u) * AMAX_STRIDE;
-    if ((threadIdx.x & 63) == 0 && m > __atomic_load_n(w, __ATOMIC_RELAXED)) atomicMax(w, m);
-}
-__device__ inline float f16_scale(uint32_t amax_bits)
-{
-    const int e = (int)((amax_bits >> 23) & 0xff);
-    if (e == 0 || e == 255) return 1.f;
-    const int se = min(max(127 + 14 - (e - 127), 27), 227);
-    return __builtin_bit_cast(float, (uint32_t)se << 23);
-}
-__device__ inline void split2h(float a, float b, uint32_t &p0, uint32_t &p1)
-{
-    // h = RNE fp16 of the pair; l = fp16 of the exact residuals a - h (v_fma_mix_f32 reads the fp16 halves in place: no v_cvt_f32_f16)
-    float ra, rb;
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p0) : "v"(a), "v"(b));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(ra) : "v"(a), "v"(p0));
-    asm("v_fma_mix_f32 %0, %1, 1.0, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "=v"(rb) : "v"(b), "v"(p0));
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(p1) : "v"(ra), "v"(rb));
-}
-template <int NPROD, typename V4> __device__ inline void split8s(const V4 &lo, const V4 &hi, float s, bf16x8 &f0, bf16x8 &f1, bf16x8 &f2)
-{
-#ifdef VIT_EXP_NOSPLIT   /* experiment builds only (tools/exp_nosplit.sh): see vit_gemm_x6.hip */
-    if (NPROD == 2) { f0 = __builtin_bit_cast(bf16x8, lo); f1 = __builtin_bit_cast(bf16x8, hi); return; }
-#endif
-    if constexpr (NPROD == 2) {
-        uint4 q0, q1;
-        split2h(lo.x * s, lo.y * s, q0.x, q1.x);
-        split2h(lo.z * s, lo.w * s, q0.y, q1.y);
-        split2h(hi.x * s, hi.y * s, q0.z, q1.z);
-        split2h(hi.z * s, hi.w * s, q0.w, q1.w);
-        f0 = __builtin_bit_cast(bf16x8, q0); f1 = __builtin_bit_cast(bf16x8, q1); f2 = f1;
-    } else {
-        split8(lo, hi, f0, f1, f2);
-    }
-}
-template <int NPROD> __device__ inline f32x16 mma(const bf16x8 &a, const bf16x8 &b, const f32x16 &c)
-{
-    if constexpr (NPROD == 2) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-    else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-// same walk as vit_gemm_x6.hip's: XCD x owns a contiguous range of the tile sequence, the sequence walks groups of 8
-// row tiles column by column
-__device__ inline void tile_of_block(int bid, int tiles_m, int tiles_n, int &tm, int &tn)
-{
-    constexpr int GM = 8;
-    const int ntiles = tiles_m * tiles_n, q = ntiles >> 3, r = ntiles & 7;
-    const int xcd = bid & 7, local = bid >> 3;
-    const int pid = xcd * q + min(xcd, r) + local;
-    const int per_group = GM * tiles_n;
-    const int group = pid / per_group, first_m = group * GM;
-    const int gsz = min(tiles_m - first_m, GM);
-    const int in_group = pid - group * per_group;
-    tm = first_m + in_group % gsz;
-    tn = in_group / gsz;
-}
-
 typedef __attribute__((address_space(3))) void *lptr_t;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Fragment reads are inline asm: a compiler-visible ds_read behind an LDS-DMA makes hipcc wait for vmcnt(0) -- for the
 // youngest DMA -- before it (it cannot tell the ring's stages apart), which would serialise the ring.  The asm reads
@@ -196,7 +85,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) k_linear_x6r(const float *_
 #if defined(__HIP_DEVICE_COMPILE__)   // (the host pass only needs the launch stub; it has no amdgcn builtins / asm constraints)
     constexpr int NW = WM * WN, RM = BM / WM / 32, RN = BN / WN / 32;
     float sx = 1.f, ix = 1.f, iw = 1.f;           // f16x3: activation scale (applied at the fragment split), inverse scales of the epilogue
-    if constexpr (NPROD == 2) { sx = f16_scale(amax_line(amax_x)); ix = 1.f / sx; iw = 1.f / f16_scale(amax_line(amax_w)); }
+    if constexpr (NPROD == 2) { sx = f16_scale_of(amax_word_read(amax_x)); ix = 1.f / sx; iw = 1.f / f16_scale_of(amax_word_read(amax_w)); }
     constexpr int A_BYTES = BM * 64, B_BYTES = BN * 96, ST_BYTES = A_BYTES + B_BYTES;
     constexpr int A_CH = BM / 16, B_CH = 6 * (BN / 64), CH = A_CH + B_CH, CPW = (CH + NW - 1) / NW;   // 1 KiB DMA chunks per stage, per wave
     static_assert(BM % 64 == 0 && BN % 64 == 0 && RM >= 1 && (RN == 1 || RN == 2), "tile shape");
@@ -339,7 +228,7 @@ __global__ void __launch_bounds__(64 * WM * WN, OCC) k_linear_x6r(const float *_
         }
     }
     if (amax_out) {             // |max| of the stored values (see vit_x6_set_output_amax): one atomic per wave
-        amax_fold(amax_out, omax);
+        amax_word_fold(amax_out, omax, blockIdx.x + 7u * blockIdx.y);
     }
 #endif
 }
@@ -382,7 +271,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 1) k_linear_x6c(const float *__r
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     float sx = 1.f, ix = 1.f, iw = 1.f;           // f16x3: activation scale (applied by the converter), inverse scales of the epilogue
-    if constexpr (NPROD == 2) { sx = f16_scale(amax_line(amax_x)); ix = 1.f / sx; iw = 1.f / f16_scale(amax_line(amax_w)); }
+    if constexpr (NPROD == 2) { sx = f16_scale_of(amax_word_read(amax_x)); ix = 1.f / sx; iw = 1.f / f16_scale_of(amax_word_read(amax_w)); }
     constexpr int NW = WM * WN, RM = BM / WM / 32, RN = BN / WN / 32;
     constexpr int RAW_BYTES = BM * 64, B_BYTES = BN * 96, AC_BYTES = BM * 96;
     constexpr int RAW0 = 0, B0 = 3 * RAW_BYTES, AC0 = B0 + 2 * B_BYTES, LDS_BYTES = AC0 + 2 * AC_BYTES;   // raw ring of 3
@@ -521,7 +410,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 1) k_linear_x6c(const float *__r
                     const int blk = i * RN + j;
                     if (blk >= 4) {               // one quarter of the split rides in this block's six MFMA gaps
                         const float c0 = blk == 4 ? clo.x : blk == 5 ? clo.z : blk == 6 ? chi.x : chi.z, c1 = blk == 4 ? clo.y : blk == 5 ? clo.w : blk == 6 ? chi.y : chi.w;
-                        if constexpr (NPROD == 2) split2h(c0 * sx, c1 * sx, p0[blk - 4], p1[blk - 4]);
+                        if constexpr (NPROD == 2) f16_split2_lds(c0 * sx, c1 * sx, p0[blk - 4], p1[blk - 4]);
                         else split2(c0, c1, p0[blk - 4], p1[blk - 4], p2[blk - 4]);
 #pragma unroll
                         for (int k = 0; k < 6; ++k) {
@@ -534,8 +423,8 @@ __global__ void __launch_bounds__(64 * WM * WN, 1) k_linear_x6c(const float *__r
             }
         } else {
             if constexpr (NPROD == 2) {
-                split2h(clo.x * sx, clo.y * sx, p0[0], p1[0]); split2h(clo.z * sx, clo.w * sx, p0[1], p1[1]);
-                split2h(chi.x * sx, chi.y * sx, p0[2], p1[2]); split2h(chi.z * sx, chi.w * sx, p0[3], p1[3]);
+                f16_split2_lds(clo.x * sx, clo.y * sx, p0[0], p1[0]); f16_split2_lds(clo.z * sx, clo.w * sx, p0[1], p1[1]);
+                f16_split2_lds(chi.x * sx, chi.y * sx, p0[2], p1[2]); f16_split2_lds(chi.z * sx, chi.w * sx, p0[3], p1[3]);
             } else {
                 split2(clo.x, clo.y, p0[0], p1[0], p2[0]); split2(clo.z, clo.w, p0[1], p1[1], p2[1]);
                 split2(chi.x, chi.y, p0[2], p1[2], p2[2]); split2(chi.z, chi.w, p0[3], p1[3], p2[3]);
@@ -665,7 +554,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 1) k_linear_x6c(const float *__r
         }
     }
     if (amax_out) {             // |max| of the stored values (vit_x6_set_output_amax): one atomic per wave
-        amax_fold(amax_out, omax);
+        amax_word_fold(amax_out, omax, blockIdx.x + 7u * blockIdx.y);
     }
 #endif
 }
@@ -676,8 +565,8 @@ template <int NPROD>
 __global__ void __launch_bounds__(256) k_split_block(const float *__restrict__ w, uint4 *__restrict__ packed, int rows, int cols,
                                                      int transpose, const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail)
 {
-    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_STRIDE] = amax[threadIdx.x * AMAX_STRIDE];     // the line the readers of this image take their inverse scale from
-    const float sw = NPROD == 2 ? f16_scale(amax_line(amax)) : 1.f;
+    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_WORD_STRIDE] = amax[threadIdx.x * AMAX_WORD_STRIDE];     // the line the readers of this image take their inverse scale from
+    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;
     // output rows R_ = transpose ? cols : rows, contraction length K_ = transpose ? rows : cols
     const int R_ = transpose ? cols : rows, K_ = transpose ? rows : cols, KG = K_ >> 3;
     __shared__ float s[64][65];                       // [output row][k]: 64 rows x 64 k (8 k groups)
@@ -715,10 +604,10 @@ __global__ void __launch_bounds__(256) k_split_pair(const float *__restrict__ w,
                                                     uint32_t *__restrict__ tail_t)
 {
     if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
-        const uint32_t a = amax[threadIdx.x * AMAX_STRIDE];
-        tail_f[threadIdx.x * AMAX_STRIDE] = a; tail_t[threadIdx.x * AMAX_STRIDE] = a;
+        const uint32_t a = amax[threadIdx.x * AMAX_WORD_STRIDE];
+        tail_f[threadIdx.x * AMAX_WORD_STRIDE] = a; tail_t[threadIdx.x * AMAX_WORD_STRIDE] = a;
     }
-    const float sw = NPROD == 2 ? f16_scale(amax_line(amax)) : 1.f;
+    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;
     __shared__ float s[64][65];                       // [row of w][column of w]
     const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
     if ((cols & 3) == 0) {                            // four columns per load (rows of w are 16-byte aligned)
@@ -794,8 +683,8 @@ __global__ void __launch_bounds__(256) k_split_many(const VitSplitJob *__restric
     const int rows = jb.rows, cols = jb.cols, transpose = jb.kind & 1, block = jb.kind & 2;
     const float *__restrict__ w = jb.w;
     uint4 *__restrict__ packed = static_cast<uint4 *>(jb.packed);
-    if (NPROD == 2 && local == 0 && threadIdx.x < 64) jb.tail[threadIdx.x * AMAX_STRIDE] = jb.amax[threadIdx.x * AMAX_STRIDE];
-    const float sw = NPROD == 2 ? f16_scale(amax_line(jb.amax)) : 1.f;
+    if (NPROD == 2 && local == 0 && threadIdx.x < 64) jb.tail[threadIdx.x * AMAX_WORD_STRIDE] = jb.amax[threadIdx.x * AMAX_WORD_STRIDE];
+    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(jb.amax)) : 1.f;
     const int R_ = transpose ? cols : rows, K_ = transpose ? rows : cols, KG = K_ >> 3;
     __shared__ float s[64][65];
     const int k0 = bx * 64;
@@ -837,9 +726,7 @@ int split_weights_many(const VitSplitJob *jobs_dev, int njobs, uint32_t total_bl
     if (np == 2) hipLaunchKernelGGL(x6r::k_split_many<2>, dim3(total_blocks), dim3(256), 0, stream, jobs_dev, njobs);
     else if (np == 3) hipLaunchKernelGGL(x6r::k_split_many<3>, dim3(total_blocks), dim3(256), 0, stream, jobs_dev, njobs);
     else hipLaunchKernelGGL(x6r::k_split_many<6>, dim3(total_blocks), dim3(256), 0, stream, jobs_dev, njobs);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 // both images of a Linear weight (rows x cols) in one launch: see k_split_pair.  block_f / block_t: the block layout (1) or the row layout (0)
@@ -862,9 +749,7 @@ int split_weight_pair(const float *w, void *packed_f, void *packed_t, int rows, 
         hipLaunchKernelGGL(x6r::k_split_pair<2>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_f), static_cast<uint4 *>(packed_t), rows, cols, block_f, block_t, am, tf, tt);
     } else
         hipLaunchKernelGGL(x6r::k_split_pair<6>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_f), static_cast<uint4 *>(packed_t), rows, cols, block_f, block_t, am, tf, tt);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int split_weight_block(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream)
@@ -882,9 +767,7 @@ int split_weight_block(const float *w, void *packed, int rows, int cols, int tra
         hipLaunchKernelGGL(x6r::k_split_block<2>, dim3((K_ + 63) / 64, (R_ + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, transpose, am, tail);
     } else
         hipLaunchKernelGGL(x6r::k_split_block<6>, dim3((K_ + 63) / 64, (R_ + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, transpose, am, tail);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 // cfg: 1 = ring kernel, 128 x 128 tiles, 3 stages, two workgroups per CU; 2 = ring kernel, 256 x 256 tiles (8 waves);
@@ -952,9 +835,7 @@ int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const floa
         else hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
     }
 #undef X6R_ARGS
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 // The ping-pong kernel with an S-way K split whose partial tiles meet in `workspace` (x6c_workspace_bytes): S = 1 needs none.
@@ -995,8 +876,6 @@ int linear_x6c_fwd(const float *x, const void *wp, const float *bias, const floa
     if (splits > 1 && hipMemsetAsync(tickets, 0, (size_t)tiles * sizeof(int), stream) != hipSuccess) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
     if (act) hipLaunchKernelGGL((x6r::k_linear_x6c<1, 256, 256, 2, 4>), dim3(tiles, splits), dim3(512), 0, stream, x, w4, bias, residual, out, pre, M, N, K, slabs, tickets, nullptr, nullptr, nullptr);
     else hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4>), dim3(tiles, splits), dim3(512), 0, stream, x, w4, bias, residual, out, pre, M, N, K, slabs, tickets, nullptr, nullptr, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

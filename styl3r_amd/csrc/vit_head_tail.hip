@@ -20,24 +20,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 namespace ht {
-__device__ inline uint4 philox4x32_10(uint4 ctr, uint2 key)      // identical to vit_resample.hip's (the two must agree bit for bit)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-        key.x += 0x9E3779B9u; key.y += 0xBB67AE85u;
-    }
-    return ctr;
-}
-
 // a(h) for four elements and the factor a'(h) (0 or scale) of each
 template <bool DROP>
 __device__ inline void activate(const float4 v, int64_t i4, uint32_t thresh, float scale, uint64_t seed, float4 &a, float4 &m)
@@ -218,9 +204,7 @@ int head_tail_fwd(const float *h, const float *w, const float *bias, float *y, i
     if (CO == 3) { if (p > 0.f) VIT_HT_F(3, true); else VIT_HT_F(3, false); }
     else { if (p > 0.f) VIT_HT_F(8, true); else VIT_HT_F(8, false); }
 #undef VIT_HT_F
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int head_tail_bwd(const float *h, const float *w, const float *dy, float *dh, float *dw, float *db, int B, int C, int CO, int64_t HW, float p,
@@ -241,8 +225,6 @@ int head_tail_bwd(const float *h, const float *w, const float *dy, float *dh, fl
     if (CO == 3) { if (p > 0.f) VIT_HT_B(3, true); else VIT_HT_B(3, false); }
     else { if (p > 0.f) VIT_HT_B(8, true); else VIT_HT_B(8, false); }
 #undef VIT_HT_B
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

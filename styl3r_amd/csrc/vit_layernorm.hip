@@ -16,10 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
 uint32_t *x6_take_output_amax();                                 // vit_gemm_x6.hip
 
 namespace {
@@ -38,13 +37,11 @@ __device__ inline uint32_t abs_bits4(const float4 &o)
     return max(max(__builtin_bit_cast(uint32_t, o.x) & 0x7fffffffu, __builtin_bit_cast(uint32_t, o.y) & 0x7fffffffu),
                max(__builtin_bit_cast(uint32_t, o.z) & 0x7fffffffu, __builtin_bit_cast(uint32_t, o.w) & 0x7fffffffu));
 }
-__device__ inline void publish_amax(uint32_t *amax_out, uint32_t m, int lane)     // one guarded atomic per wave, spread over the 64-word line
+
+__device__ inline void publish_amax(uint32_t *amax_out, uint32_t m)     // the |max| word of the stored values, if the caller asked for one
 {
     if (!amax_out) return;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
-    uint32_t *w = amax_out + ((blockIdx.x + (threadIdx.x >> 6)) & 63u) * 32;      // (64 slots, one per 128-byte line: vit_gemm_x6.hip AMAX_STRIDE)
-    if (lane == 0 && m > __atomic_load_n(w, __ATOMIC_RELAXED)) atomicMax(w, m);
+    amax_word_fold(amax_out, m, blockIdx.x);
 }
 
 template <int N4>
@@ -86,7 +83,7 @@ __global__ void __launch_bounds__(256) k_ln_fwd(const float *__restrict__ x, con
         }
         if (lane == 0) { mean[row] = mu; rstd[row] = rs; }
     }
-    publish_amax(amax_out, omax, lane);
+    publish_amax(amax_out, omax);
 }
 
 // Two LayerNorms of one shape in one launch (blockIdx.y = group): the dual decoders of the serving path (vit_layernorm_fwd_grouped).  Rows of
@@ -129,7 +126,7 @@ __global__ void __launch_bounds__(256) k_ln_fwd_grouped(const LnGroups a, int M,
             omax = max(omax, abs_bits4(o));
         }
     }
-    publish_amax(amax_out, omax, lane);
+    publish_amax(amax_out, omax);
 }
 
 template <int N4>
@@ -177,7 +174,7 @@ __global__ void __launch_bounds__(256) k_ln_bwd(const float *__restrict__ dy, co
             omax = max(omax, abs_bits4(o));
         }
     }
-    publish_amax(amax_out, omax, lane);
+    publish_amax(amax_out, omax);
     // column sums of the workgroup -> partial[blockIdx.x][0..C) = dgamma, [C..2C) = dbeta
     if (wave > 0) {
 #pragma unroll
@@ -244,9 +241,7 @@ int layernorm_fwd(const float *x, const float *gamma, const float *beta, float *
 #define VIT_LN_F(N4) case N4: hipLaunchKernelGGL(k_ln_fwd<N4>, dim3(blocks), dim3(256), 0, stream, x, gamma, beta, y, mean, rstd, M, eps, am_out); break
     switch (C / 256) { VIT_LN_F(1); VIT_LN_F(2); VIT_LN_F(3); VIT_LN_F(4); VIT_LN_F(5); VIT_LN_F(6); VIT_LN_F(7); VIT_LN_F(8); }
 #undef VIT_LN_F
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int layernorm_fwd_grouped(const float *const *x, const float *const *gamma, const float *const *beta, float *const *y, int groups, int M, int C,
@@ -265,9 +260,7 @@ int layernorm_fwd_grouped(const float *const *x, const float *const *gamma, cons
 #define VIT_LN_G(N4) case N4: hipLaunchKernelGGL(k_ln_fwd_grouped<N4>, dim3(blocks, groups), dim3(256), 0, stream, a, M, eps, am_out); break
     switch (C / 256) { VIT_LN_G(1); VIT_LN_G(2); VIT_LN_G(3); VIT_LN_G(4); VIT_LN_G(5); VIT_LN_G(6); VIT_LN_G(7); VIT_LN_G(8); }
 #undef VIT_LN_G
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int layernorm_bwd(const float *dy, const float *x, const float *mean, const float *rstd, const float *gamma, const float *dskip,
@@ -282,8 +275,6 @@ int layernorm_bwd(const float *dy, const float *x, const float *mean, const floa
     switch (C / 256) { VIT_LN_B(1); VIT_LN_B(2); VIT_LN_B(3); VIT_LN_B(4); VIT_LN_B(5); VIT_LN_B(6); VIT_LN_B(7); VIT_LN_B(8); }
 #undef VIT_LN_B
     hipLaunchKernelGGL(k_ln_param_reduce, dim3(2 * C / 32), dim3(256), 0, stream, scratch, dgamma, dbeta, blocks, C, accumulate);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

@@ -17,11 +17,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 namespace {
 struct Coef { float lr_wd, b1, b2, eps, step_size, sqrt_bc2, scale; };
 
@@ -86,12 +84,7 @@ __global__ void __launch_bounds__(256) k_adamw(const VitAdamChunk *__restrict__ 
             seen(P);
         }
     }
-    if (ch.amax) {              // (workgroup-uniform) 64 slots, one per 128-byte line: csrc/vit_gemm_x6.hip amax_fold
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pm = max(pm, (uint32_t)__shfl_xor((int)pm, o, 64));
-        uint32_t *w = ch.amax + ((blockIdx.x + (threadIdx.x >> 6)) & 63u) * 32;
-        if ((threadIdx.x & 63) == 0 && pm > __atomic_load_n(w, __ATOMIC_RELAXED)) atomicMax(w, pm);
-    }
+    if (ch.amax) amax_word_fold(ch.amax, pm, blockIdx.x);      // (workgroup-uniform)
 }
 }  // namespace
 
@@ -102,8 +95,6 @@ int adamw_step(const VitAdamChunk *chunks, int n_chunks, float lr, float beta1, 
     if (!chunks || n_chunks < 0 || !(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return VIT_EINVAL;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_adamw, dim3(n_chunks), dim3(256), 0, stream, chunks, lr, beta1, beta2, eps, weight_decay, grad_scale);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

@@ -7,11 +7,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 #pragma clang fp contract(off)
 // ADD: out = upsample(in) + max(addend, 0) -- the 'gs' head's `feat_up(path_1) + input_merger(imgs)` (dpt_gs_head.py:146-148) with the
 // input merger's ReLU applied while its pre-activation is read, in the same pass that writes the up-sampled map
@@ -246,9 +244,7 @@ int upsample2x_bwd(const float *dout, float *din, int64_t planes, int H, int W, 
     else
         hipLaunchKernelGGL(k_upsample2x_bwd, dim3((unsigned)(blocks > 65536 * 16 ? 65536 * 16 : blocks)), dim3(256), 0, stream, dout, din,
                            planes, H, W, rh, rw);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int upsample2x_fwd(const float *in, float *out, int64_t planes, int H, int W, hipStream_t stream)
@@ -266,9 +262,7 @@ int upsample2x_fwd(const float *in, float *out, int64_t planes, int H, int W, hi
     } else
         hipLaunchKernelGGL(k_upsample2x<false>, dim3((unsigned)(blocks > 65536 * 16 ? 65536 * 16 : blocks)), dim3(256), 0, stream, in,
                            (const float *)nullptr, out, planes, H, W, rh, rw);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 // 3x3 / stride 1 / padding 1 patches of an NCHW tensor as pixel-major rows: cols[(b, y, x)][(tap, ci)] = f(in[b, ci, y + dy - 1, x + dx - 1])
@@ -309,9 +303,7 @@ int im2col3_rows(const float *in, float *cols, int B, int Ci, int H, int W, int 
     if (gz > 65535 || H > 65535) return VIT_EINVAL;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_im2col3_rows, dim3((W + 31) / 32, H, (unsigned)gz), dim3(256), 0, stream, in, cols, B, Ci, H, W, relu);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int upsample2x_add_relu_fwd(const float *in, const float *addend, float *out, int64_t planes, int H, int W, hipStream_t stream)
@@ -329,9 +321,7 @@ int upsample2x_add_relu_fwd(const float *in, const float *addend, float *out, in
     } else
         hipLaunchKernelGGL(k_upsample2x<true>, dim3((unsigned)(blocks > 65536 * 16 ? 65536 * 16 : blocks)), dim3(256), 0, stream, in, addend,
                            out, planes, H, W, rh, rw);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int im2col7(const float *img, float *cols, int B, int H, int W, hipStream_t stream)
@@ -341,27 +331,13 @@ int im2col7(const float *img, float *cols, int B, int H, int W, hipStream_t stre
     const int64_t blocks = (total + 255) / 256;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_im2col7, dim3((unsigned)(blocks > 65536 * 16 ? 65536 * 16 : blocks)), dim3(256), 0, stream, img, cols, B, H, W);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 // ---- ReLU -> Dropout of the 'gs_params' DPT heads (dpt_block.py:332-340: ReLU(True), Dropout(0.1)) on their 256^2 x 256-channel
 // tensors (1.3 GB at 20 views) as ONE pass each way.  Forward: y = keep(i) ? max(x, 0) / (1 - p) : 0 with keep drawn by a
 // counter-based generator (Philox-4x32-10 keyed by (seed, element index / 4): no mask tensor is written); y > 0 exactly where
 // the gradient passes, so the backward needs y only: dx = y > 0 ? g / (1 - p) : 0.  The framework runs clamp + fused_dropout
 // forward and masked_scale + threshold_backward backward, two 2.7 GB passes each way plus the mask.
-__device__ inline uint4 philox4x32_10(uint4 ctr, uint2 key)
-{
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, ctr.x), lo0 = 0xD2511F53u * ctr.x;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, ctr.z), lo1 = 0xCD9E8D57u * ctr.z;
-        ctr = make_uint4(hi1 ^ ctr.y ^ key.x, lo1, hi0 ^ ctr.w ^ key.y, lo0);
-        key.x += 0x9E3779B9u; key.y += 0xBB67AE85u;
-    }
-    return ctr;
-}
-
 __global__ void __launch_bounds__(256) k_relu_dropout_fwd(const float *__restrict__ x, float *__restrict__ y, int64_t n4, uint32_t thresh,
                                                           float scale, uint64_t seed)
 {
@@ -396,9 +372,7 @@ int relu_dropout_fwd(const float *x, float *y, int64_t n, float p, uint64_t seed
     const int64_t n4 = n >> 2;
     hipLaunchKernelGGL(k_relu_dropout_fwd, dim3((unsigned)((n4 + 255) / 256 < 256 * 64 ? (n4 + 255) / 256 : 256 * 64)), dim3(256), 0, stream, x, y, n4, thresh,
                        (float)(1.0 / keep), seed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 
 int relu_dropout_bwd(const float *y, const float *g, float *dx, int64_t n, float p, hipStream_t stream)
@@ -408,8 +382,6 @@ int relu_dropout_bwd(const float *y, const float *g, float *dx, int64_t n, float
     const int64_t n4 = n >> 2;
     hipLaunchKernelGGL(k_relu_dropout_bwd, dim3((unsigned)((n4 + 255) / 256 < 256 * 64 ? (n4 + 255) / 256 : 256 * 64)), dim3(256), 0, stream, y, g, dx, n4,
                        (float)(1.0 / (1.0 - (double)p)));
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

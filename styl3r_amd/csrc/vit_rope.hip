@@ -10,11 +10,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_common.h"
 
 namespace vit {
-extern thread_local hipError_t g_last_hip_error;
-
 #pragma clang fp contract(off)
 __global__ void __launch_bounds__(256) k_rope2d(float *__restrict__ tokens, const int64_t *__restrict__ pos,
                                                 const float *__restrict__ cos_tab, const float *__restrict__ sin_tab,
@@ -52,8 +50,6 @@ int rope2d(float *tokens, const int64_t *positions, const float *cos_tab, const 
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_rope2d, dim3(blocks), dim3(256), 0, stream, tokens, positions, cos_tab, sin_tab, N, H, Q, P, total,
                        sb, sn, sh, sign);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_last_hip_error = e; return VIT_ELAUNCH; }
-    return VIT_OK;
+    return launch_status();
 }
 }  // namespace vit

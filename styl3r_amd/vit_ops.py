@@ -46,13 +46,22 @@ ERRORS = {-1: "VIT_EINVAL", -3: "VIT_ELAUNCH"}
 _lib = None
 
 
+def _headers() -> list[Path]:
+    """every header the kernel sources may include: csrc/*.h and include/vit_ops.h"""
+    return sorted(_CSRC.glob("*.h")) + [_PKG.parent / "include" / "vit_ops.h"]
+
+
+def build_deps() -> list[Path]:
+    """the files the library stamp covers: the sources and every header they compile against (editing one rebuilds the library)"""
+    return [_CSRC / s for s in _SOURCES if (_CSRC / s).exists()] + _headers()
+
+
 def build_library(force: bool = False, verbose: bool = False) -> Path:
     """hipcc --offload-arch=gfx950 of csrc/vit_*.hip into lib/libvit_hip.so; rebuilt whenever the digest of
-    (sources, header, command line) differs from the stamp written next to the library (same scheme as _lib.py)."""
+    (sources, headers, command line) differs from the stamp written next to the library (same scheme as _lib.py)."""
     from ._lib import sources_digest
     names = [s for s in _SOURCES if (_CSRC / s).exists()]
-    srcs = [_CSRC / s for s in names]
-    deps = srcs + [(_PKG.parent / "include" / "vit_ops.h")]
+    deps = build_deps()
     extra = os.environ.get("VIT_HIPCC_EXTRA", "").split()          # kernel-experiment builds (tools/ only, with VIT_LIB_NAME)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", *extra, *names, "-o", LIB_PATH.name]
     want = sources_digest(deps, cmd)
@@ -68,7 +77,7 @@ def build_library(force: bool = False, verbose: bool = False) -> Path:
     objdir = _PKG.parent / "build" / "obj"
     objdir.mkdir(parents=True, exist_ok=True)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", *extra]
-    headers = sorted(_CSRC.glob("*.h")) + [(_PKG.parent / "include" / "vit_ops.h")]
+    headers = _headers()
     hdig = hashlib.sha256(b"".join(h.read_bytes() for h in headers) + " ".join(flags).encode()).hexdigest()
 
     def compile_one(name):
@@ -558,7 +567,7 @@ def _f16() -> bool:
 class _AmaxArena:
     """zero-initialised |max| "words" for vit_amax results (one per activation tensor per use).  A word is 64 int32 slots, ONE PER 128-BYTE CACHE
     LINE (8 KiB): producers fold their maxima into slot (workgroup + wave) & 63 -- atomics on one cache line serialise in the L2, thousands of
-    them cost tens of microseconds per launch -- and readers take the max over the slots (csrc/vit_gemm_x6.hip amax_fold / amax_line).  Words
+    them cost tens of microseconds per launch -- and readers take the max over the slots (csrc/vit_common.h amax_word_fold / amax_word_read).  Words
     are handed out in order from a device buffer that is replaced -- one allocation + one fill -- when it runs out; words still referenced
     (saved for a backward) keep their buffer alive"""
     LINE = 64 * 32

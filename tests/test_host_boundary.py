@@ -127,6 +127,26 @@ def test_vit_library_exports_every_declared_symbol():
     assert lib.vit_attention_fwd(C.byref(a), None, None, None, None, None, None) == -1
 
 
+def test_vit_library_stamp_covers_every_included_header():
+    """an edited header must change the stamp of libvit_hip.so, or the stale library is kept: every file a csrc/vit_*.hip
+    includes with quotes (and what those include in turn) is among vit_ops.build_deps()"""
+    from styl3r_amd import vit_ops
+    deps = {p.resolve() for p in vit_ops.build_deps()}
+    csrc = ROOT / "styl3r_amd/csrc"
+    todo = sorted(csrc.glob("vit_*.hip"))
+    assert {p.resolve() for p in todo} <= deps
+    seen = set()
+    while todo:
+        src = todo.pop()
+        for inc in re.findall(r'^\s*#\s*include\s+"([^"]+)"', src.read_text(), re.M):
+            h = (src.parent / inc).resolve()
+            assert h in deps, f"{src.name} includes {inc}, which the library stamp does not cover"
+            if h not in seen:
+                seen.add(h)
+                todo.append(h)
+    assert (csrc / "vit_common.h").resolve() in seen
+
+
 def test_vit_ops_reject_cpu_tensors():
     from styl3r_amd import vit_ops
     with pytest.raises(RuntimeError, match="no CPU path"):
