@@ -4,7 +4,8 @@ rope2d   restates rope_2d_cpu, src/model/encoder/backbone/croco/curope/curope.cp
          (four quarters [u_Y, v_Y, u_X, v_X], inv_freq = fwd / base^(d/Q)); pinned by golden
          vectors produced from the reference's own RoPE2D (tests/golden/make_vit_fixtures.py).
 attention restates memory_efficient_attention's contract softmax(q k^T scale) v on (B,N,H,D)
-         (xformers 0.0.24, call sites blocks.py:129,195), evaluated in float64.
+         (xformers 0.0.24, call sites blocks.py:129,195), evaluated in float64 (dtype=np.float32: the same
+         formulas in fp32, the yardstick of what fp32 arithmetic itself achieves on an input).
 """
 import numpy as np
 
@@ -24,23 +25,23 @@ def rope2d(tokens_bnhd, positions, base=100.0, fwd=1.0, dtype=np.float64):
     return t
 
 
-def attention(q, k, v, scale):
-    q, k, v = (np.asarray(x, dtype=np.float64) for x in (q, k, v))
-    s = np.einsum("bqhd,bkhd->bhqk", q, k) * scale
+def attention(q, k, v, scale, dtype=np.float64):
+    q, k, v = (np.asarray(x, dtype=dtype).transpose(0, 2, 1, 3) for x in (q, k, v))      # (b,h,n,d): batched matmuls
+    s = (q @ k.swapaxes(-1, -2)) * dtype(scale)
     s = s - s.max(-1, keepdims=True)
     p = np.exp(s)
-    lse_shift = np.log(p.sum(-1))
     p = p / p.sum(-1, keepdims=True)
-    return np.einsum("bhqk,bkhd->bqhd", p, v), p
+    return (p @ v).transpose(0, 2, 1, 3), p
 
 
-def attention_backward(q, k, v, scale, g):
-    q, k, v, g = (np.asarray(x, dtype=np.float64) for x in (q, k, v, g))
-    o, p = attention(q, k, v, scale)
-    dv = np.einsum("bhqk,bqhd->bkhd", p, g)
-    dp = np.einsum("bqhd,bkhd->bhqk", g, v)
+def attention_backward(q, k, v, scale, g, dtype=np.float64, return_ds=False):
+    q, k, v, g = (np.asarray(x, dtype=dtype) for x in (q, k, v, g))
+    o, p = attention(q, k, v, scale, dtype)
+    qt, kt, vt, gt = (x.transpose(0, 2, 1, 3) for x in (q, k, v, g))
+    dv = (p.swapaxes(-1, -2) @ gt).transpose(0, 2, 1, 3)
+    dp = gt @ vt.swapaxes(-1, -2)
     delta = (g * o).sum(-1).transpose(0, 2, 1)[..., None]      # (b,h,q,1)
-    ds = p * (dp - delta) * scale
-    dq = np.einsum("bhqk,bkhd->bqhd", ds, k)
-    dk = np.einsum("bhqk,bqhd->bkhd", ds, q)
-    return dq, dk, dv
+    ds = p * (dp - delta) * dtype(scale)
+    dq = (ds @ kt).transpose(0, 2, 1, 3)
+    dk = (ds.swapaxes(-1, -2) @ qt).transpose(0, 2, 1, 3)
+    return (dq, dk, dv, o, ds) if return_ds else (dq, dk, dv)

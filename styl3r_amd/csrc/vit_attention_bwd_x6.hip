@@ -206,14 +206,18 @@ __device__ inline void t_times_regs(const unsigned char *__restrict__ img, int c
 // two halves of the same column).  Returns the scale to split them with; when the column's |max| has outgrown the scale so far, the lane's
 // accumulators (lo, hi: everything accumulated under the old scale) are multiplied by new / old first -- exact, powers of two.  The scale only
 // ever shrinks (a larger |max| wins), so a lane rescales a handful of times at the start of its walk and then never again.
+// A column max with exponent field 0 -- an all-zero tile, or one whose largest |dS| is an fp32 subnormal (probabilities ~100 nats below the
+// row's log-sum-exp times a small dO) -- leaves the scale alone: f16_scale_of returns 1 for it, and a scale of 1 kept for the rest of the walk
+// would round every later dS of the lane to zero in fp16 whenever the gradient is small (dO ~ 1e-6).  Such a tile's own dS is then split at
+// the running scale (<= 2^100) and mostly underflows fp16: a loss below 2^-126 per term.
 __device__ inline float ds_running_scale(const f32x16 &ds, float &s_run, f32x16 &lo, f32x16 &hi)
 {
     uint32_t m = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) m = max(m, abs_bits(ds[r]));
     m = max(m, (uint32_t)__shfl_xor((int)m, 32, 64));                 // the column's other half
-    const float s_new = fminf(s_run, f16_scale_of(m));                // f16_scale_of(0) = 1: an all-zero tile changes nothing below 1 ...
-    if (m != 0u && s_new != s_run) {                                  // (per lane; rare)
+    const float s_new = fminf(s_run, f16_scale_of(m));
+    if ((m >> 23) != 0u && s_new != s_run) {                          // (per lane; rare)
         const float f = s_new / s_run;
 #pragma unroll
         for (int r = 0; r < 16; ++r) { lo[r] *= f; hi[r] *= f; }
@@ -257,7 +261,8 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_q_x6(VitAttnArgs a, const f
     // f16x3: power-of-two operand scales from the tensors' |max| words; the products are un-scaled right behind their MFMAs
     float sk = 1.f, sv = 1.f, sg = 1.f, sq = 1.f, inv_qk = 1.f, inv_gv = 1.f, s_run = 1.2676506e30f /* 2^100: no dS seen yet */;
     if (NP == 2) {
-        sq = f16_scale_of(amax_word_read(a.amax_q)); sk = f16_scale_of(amax_word_read(a.amax_k));
+        sq = f16_scale_of(amax_word_read(a.amax_q)) * f16_prescale_headroom(a.scale * LOG2E);     // (Q is split after the scale * log2 e)
+        sk = f16_scale_of(amax_word_read(a.amax_k));
         sv = f16_scale_of(amax_word_read(a.amax_v)); sg = f16_scale_of(amax_word_read(a.amax_g));
         inv_qk = 1.f / (sq * sk); inv_gv = 1.f / (sg * sv);
     }
@@ -338,7 +343,8 @@ __global__ void __launch_bounds__(256, 2) k_attn_bwd_kv_x6(VitAttnArgs a, const 
     float sk = 1.f, sv = 1.f, sg = 1.f, sq = 1.f, inv_qk = 1.f, inv_gv = 1.f, s_run = 1.2676506e30f /* 2^100: no dS seen yet */;
     constexpr float PSCALE = 16384.f;       // f16x3: the probabilities' scale (p <= 1)
     if (NP == 2) {
-        sq = f16_scale_of(amax_word_read(a.amax_q)); sk = f16_scale_of(amax_word_read(a.amax_k));
+        sq = f16_scale_of(amax_word_read(a.amax_q));
+        sk = f16_scale_of(amax_word_read(a.amax_k)) * f16_prescale_headroom(a.scale * LOG2E);     // (K is split after the scale * log2 e)
         sv = f16_scale_of(amax_word_read(a.amax_v)); sg = f16_scale_of(amax_word_read(a.amax_g));
         inv_qk = 1.f / (sq * sk); inv_gv = 1.f / (sg * sv);
     }

@@ -46,11 +46,12 @@ __global__ void __launch_bounds__(256, 2) k_attn_fwd_x6(VitAttnArgs a, const flo
     const int qi = min(q0 + col, a.Nq - 1);   // clamped: rows beyond Nq compute garbage that is never stored
     const bool wave_active = q0 < a.Nq;
     float qscale = a.scale * 1.4426950408889634f;   // scores in the base-2 domain
-    // f16x3: tensor scales (a rotation grows a component by at most sqrt 2: |max| s < 2^15.5, inside fp16's 65 504) and the two inverse factors
+    // f16x3: tensor scales (a rotation grows a component by at most sqrt 2: |max| s < 2^15.5, inside fp16's 65 504; Q is split after its
+    // multiplication by qscale, so its power of two leaves room for that factor too: f16_prescale_headroom) and the two inverse factors
     float sk = 1.f, sv = 1.f, inv_qk = 1.f, inv_pv = 1.f;
     constexpr float PSCALE = 16384.f;
     if (NP == 2) {
-        const float sq = f16_scale_of(amax_word_read(a.amax_q));
+        const float sq = f16_scale_of(amax_word_read(a.amax_q)) * f16_prescale_headroom(qscale);
         sk = f16_scale_of(amax_word_read(a.amax_k)); sv = f16_scale_of(amax_word_read(a.amax_v));
         qscale *= sq;
         inv_qk = 1.f / (sq * sk); inv_pv = 1.f / (PSCALE * sv);

@@ -71,6 +71,14 @@ __device__ inline float f16_scale_of(uint32_t amax_bits)
     const int se = min(max(127 + 14 - (e - 127), 27), 227);       // s in [2^-100, 2^100]
     return __builtin_bit_cast(float, (uint32_t)se << 23);
 }
+// The extra power of two for an operand that is split AFTER a multiplication by a constant c (the attention's Q or K times scale * log2 e):
+// |max| s |c| stays below 2^15 (2^15.5 with a RoPE rotation, still inside fp16's 65 504).  1 for |c| < 1 -- scale < 0.69, every model call --
+// so the operand's power of two is f16_scale_of's own there; 2^-(e+1) for |c| in [2^e, 2^(e+1)).
+__device__ inline float f16_prescale_headroom(float c)
+{
+    const int e = min((int)((__builtin_bit_cast(uint32_t, c) >> 23) & 0xff) - 127, 100);
+    return e < 0 ? 1.f : __builtin_bit_cast(float, (uint32_t)(126 - e) << 23);
+}
 // Two (scaled) fp32 values -> their two fp16 pieces, each packed (low half = first value): h = RNE fp16, l = fp16 of the exact residual
 // (a - h is exact in fp32).  Two functions, the same bits:
 //   f16_split2      plain vector conversions: safe for pieces that feed an MFMA straight from registers.  The compiler only inserts the

@@ -61,3 +61,19 @@ def assert_close_rel(actual, expected, rel=1e-4, what="", atol=0.0):
     if os.environ.get("PARITY_VERBOSE"):      # bar calibration runs: `PARITY_VERBOSE=1 pytest -s` lists every observed distance beside its bar
         print(f"    [parity] {what}: rel {err / scale:.3e} (bar {rel:.1e})")
     assert err <= rel * scale + atol, f"{what}: max abs err {err:.3e} vs scale {scale:.3e} (rel {err / scale:.3e})"
+
+
+def worst_row_rel(actual, expected, floor=1e-300):
+    """per-ROW error of a (B, N, H, D) attention tensor: a row is one (b, h, n) -- (b, h, query) for out / dq, (b, h, key) for dk / dv.
+    Error of a row = max |a - e| over the row / max |e| over the row, so a row far below the tensor's maximum is judged at its own scale;
+    rows whose reference max is below `floor` (a number, or one value per row: shape (B, N, H)) -- exactly zero ones in particular -- are
+    divided by `floor` instead.  A NaN / Inf counts as an
+    infinite error.  Returns (worst error, (b, h, n) of that row)."""
+    a = np.asarray(actual, dtype=np.float64); e = np.asarray(expected, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        err = np.abs(a - e).max(-1)
+    err = np.where(np.isfinite(err), err, np.inf)
+    den = np.maximum(np.abs(e).max(-1), floor)
+    rel = err / den
+    i = np.unravel_index(int(np.argmax(rel)), rel.shape)
+    return float(rel[i]), (int(i[0]), int(i[2]), int(i[1]))

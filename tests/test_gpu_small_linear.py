@@ -244,3 +244,34 @@ def test_narrow_outputs_take_the_barrier_free_kernel_at_train_step_row_counts(M,
     bar = BAR[mode]
     assert _rel(y.detach(), ref.detach()) <= bar
     assert _rel(x.grad, dx_ref) <= 3 * bar and _rel(w.grad, wd.grad) <= 3 * bar and _rel(b.grad, bd.grad) <= 3 * bar
+
+
+# own-scale bar of the SMALLER problem of a two-problem f16x3 launch whose input sits 2^12 below the other's: the shared |max| word puts its
+# operand at 2^2 .. 2^3 in fp16 units instead of 2^14 .. 2^15.  Measured 2.3e-7 (problem 0: 2.3e-7, bf16x6 3.0e-7 on both): the shared word
+# costs nothing at this distance, so the bar is the file's own
+GROUPED_SMALL_BAR = BAR["f16x3"]
+
+
+def test_grouped_launch_two_magnitudes_each_problem_at_its_own_scale(vo, monkeypatch):
+    """vit_linear_sm_grouped in f16x3 with x1 = 2^-12 x0: ONE |max| word (the stacked input's) scales both problems; each is measured against
+    float64 at its own scale -- problem 0 against the file's BAR, problem 1 against GROUPED_SMALL_BAR, beside bf16x6 on the same input"""
+    from torch import nn
+    g = torch.Generator(DEV).manual_seed(13)
+    M, K, N = 257, 768, 2304
+    x = torch.randn(2, M, K, device=DEV, generator=g)
+    x[1] *= 2.0 ** -12
+    layers = [nn.Linear(K, N).to(DEV), nn.Linear(K, N).to(DEV)]
+    for l in layers:
+        l.bias.data.zero_()                    # (a bias at unit scale would set problem 1's output scale)
+    refs = [x[i].double() @ layers[i].weight.detach().double().t() for i in range(2)]
+    errs = {}
+    with torch.no_grad():
+        assert vo.grouped_ok(x, N)
+        for mode in ("bf16x6", "f16x3"):
+            monkeypatch.setattr(vo, "LINEAR_MODE", mode)
+            got = vo.grouped_linear(x, layers)
+            assert torch.isfinite(got).all()
+            errs[mode] = [_rel(got[i], refs[i]) for i in range(2)]
+    print("grouped launch, x1 = 2^-12 x0, error at each problem's own scale (problem 0, problem 1):", errs)
+    assert errs["f16x3"][0] <= BAR["f16x3"] and errs["bf16x6"][0] <= BAR["bf16x6"] and errs["bf16x6"][1] <= BAR["bf16x6"]
+    assert errs["f16x3"][1] <= GROUPED_SMALL_BAR, errs
