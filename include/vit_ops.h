@@ -356,6 +356,33 @@ int vit_adapter_fwd(const VitAdapterArgs *a, float *means, float *cov, float *sh
 int vit_adapter_bwd(const VitAdapterArgs *a, const float *d_means, const float *d_cov, const float *d_sh, const float *d_opac,
                     float *d_pts0, float *d_ptsr, float *d_par0, float *d_parr, float *d_app, void *stream);
 
+/*
+ * The tail of LPIPS-VGG (loss_lpips.py:27-54; csrc/vit_lpips.hip has the arithmetic and the byte model): over up to five feature taps
+ * k of N images each,
+ *     dist[n] = sum_k mean_hw sum_c w_k[c] (a^_c - b^_c)^2,   a^ = a / (sqrt(sum_c a_c^2) + 1e-10),  a = tap k of fa, b = of fb,
+ * taps NCHW fp32 (N, C_k, H_k, W_k), w_k (C_k).  relu_in != 0: the taps are pre-activations, max(x, 0) is applied on load (and the
+ * backward applies the ReLU mask).  vit_lpips_fwd: one launch over all taps + one fold per image; scratch: vit_lpips_scratch_bytes
+ * (per-workgroup partials, folded in index order: bit-identical run to run, no atomics).  stats (16-byte aligned, vit_lpips_stats_bytes:
+ * 16 B per pixel) or NULL: per-pixel statistics for the backward.  vit_lpips_bwd: dfa_k = d(sum_n g[n] dist[n]) / d fa_k for every tap in
+ * one launch, g (N) device-resident; fb gets no gradient (ground truth).  Both return VIT_EINVAL before launching on a bad table.
+ */
+typedef struct VitLpipsTap {
+    const float *fa, *fb, *w;
+    float *dfa;                 /* backward output (the shape of fa); ignored by the forward */
+    int32_t C, H, W;
+} VitLpipsTap;
+size_t vit_lpips_scratch_bytes(const VitLpipsTap *taps, int n_taps, int N);
+size_t vit_lpips_stats_bytes(const VitLpipsTap *taps, int n_taps, int N);
+int vit_lpips_fwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, float *dist, void *scratch, float *stats, void *stream);
+int vit_lpips_bwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, const float *g, const float *stats, void *stream);
+
+/*
+ * nn.MaxPool2d(2, 2) of LPIPS's VGG16 on (planes, H, W) maps, H and W even, `in` / `din` 8-byte aligned.  The backward recomputes the
+ * argmax from the input (no index tensor; the framework's rule: first maximum in row-major order, a NaN wins) and overwrites din.
+ */
+int vit_maxpool2x2_fwd(const float *in, float *out, int64_t planes, int H, int W, void *stream);
+int vit_maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, void *stream);
+
 const char *vit_version(void);
 const char *vit_last_error(void);
 

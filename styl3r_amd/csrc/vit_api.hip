@@ -58,6 +58,12 @@ int split_weight_pair(const float *w, void *packed_f, void *packed_t, int rows, 
 int split_weights_many(const VitSplitJob *jobs_dev, int njobs, uint32_t total_blocks, hipStream_t stream);
 int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
                    int K, int act, int cfg, hipStream_t stream);
+size_t lpips_scratch_bytes(const VitLpipsTap *taps, int n_taps, int N);
+size_t lpips_stats_bytes(const VitLpipsTap *taps, int n_taps, int N);
+int lpips_fwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, float *dist, void *scratch, float *stats, hipStream_t stream);
+int lpips_bwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, const float *g, const float *stats, hipStream_t stream);
+int maxpool2x2_fwd(const float *in, float *out, int64_t planes, int H, int W, hipStream_t stream);
+int maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, hipStream_t stream);
 int linear_sm_set(int max_rows, int tm, int nw);
 int linear_sm_ok(int M, int N, int K);
 int linear_sm_grouped(const float *const *x, const void *const *wpb, const float *const *bias, const float *const *residual, float *const *out,
@@ -277,6 +283,29 @@ VIT_EXPORT int vit_adapter_bwd(const VitAdapterArgs *a, const float *d_means, co
                                void *stream)
 {
     return vit::adapter_bwd(a, d_means, d_cov, d_sh, d_opac, d_pts0, d_ptsr, d_par0, d_parr, d_app, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT size_t vit_lpips_scratch_bytes(const VitLpipsTap *taps, int n_taps, int N) { return vit::lpips_scratch_bytes(taps, n_taps, N); }
+VIT_EXPORT size_t vit_lpips_stats_bytes(const VitLpipsTap *taps, int n_taps, int N) { return vit::lpips_stats_bytes(taps, n_taps, N); }
+
+VIT_EXPORT int vit_lpips_fwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, float *dist, void *scratch, float *stats, void *stream)
+{
+    return vit::lpips_fwd(taps, n_taps, N, relu_in, dist, scratch, stats, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT int vit_lpips_bwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, const float *g, const float *stats, void *stream)
+{
+    return vit::lpips_bwd(taps, n_taps, N, relu_in, g, stats, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT int vit_maxpool2x2_fwd(const float *in, float *out, int64_t planes, int H, int W, void *stream)
+{
+    return vit::maxpool2x2_fwd(in, out, planes, H, W, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT int vit_maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, void *stream)
+{
+    return vit::maxpool2x2_bwd(in, dout, din, planes, H, W, static_cast<hipStream_t>(stream));
 }
 
 VIT_EXPORT const char *vit_version(void) { return "vit-hip gfx950 0.1.0"; }

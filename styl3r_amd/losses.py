@@ -8,8 +8,10 @@ Mirrors
 torchvision is not installed and the ImageNet VGG19 weights cannot be downloaded: `VGGEncoder` rebuilds the
 `vgg19().features[:21]` stack with torchvision's parameter names (`N.weight`, N in 0,2,5,7,10,12,14,16,19), so
 `load_vgg19_features(state_dict)` accepts the stock `vgg19-dcbb9e9d.pth` when it is available; until then the
-weights are random and only the arithmetic is testable.  LPIPS (loss_lpips.py) needs its own learned weights too
-and is not built.  The convolutions run on MIOpen in fp32.
+weights are random and only the arithmetic is testable.  LPIPS (loss_lpips.py) needs its own learned weights too:
+`LPIPS.load_lpips_weights` takes the `lpips` package's `vgg.pth` and torchvision's vgg16 features when they are available.
+On the GPU (fp32 device tensors, a split-arithmetic mode of vit_ops) LPIPS runs on the HIP kernels: the VGG16 convolutions on
+Conv2dX6 with their ReLUs folded in, vit_maxpool2x2 and the fused tail vit_lpips_fwd / _bwd; elsewhere the plain expression.
 """
 from __future__ import annotations
 
@@ -20,6 +22,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch import Tensor
 
+from . import vit_ops
 from .vit_ops import Conv2dX6   # nn.Conv2d on the CPU; bf16x6 implicit-GEMM kernels for eligible layers on the GPU
 
 _VGG19_CFG = [64, 64, "M", 128, 128, "M", 256, 256, 256, 256, "M", 512]   # features[:21] ends after relu4_1
@@ -218,6 +221,21 @@ class _LpipsVgg16(nn.Module):
             feats.append(x)
         return feats
 
+    def preacts(self, x):
+        """the five taps BEFORE their ReLU (device route): every ReLU is folded into what reads its output -- the next convolution
+        (Conv2dX6.forward_fused: conv of relu(x); for the 64-channel conv1_2 on the library path that is one framework ReLU), the
+        max-pool (pools the pre-activations: max commutes with ReLU) and vit_lpips_fwd (relu_in) -- so no ReLU'd copy is stored."""
+        feats, first = [], True
+        for s in range(1, 6):
+            for m in getattr(self, f"slice{s}"):
+                if isinstance(m, nn.MaxPool2d):
+                    x = vit_ops.maxpool2x2(x)
+                elif isinstance(m, Conv2dX6):
+                    x = m(x) if first else m.forward_fused(x)
+                    first = False
+            feats.append(x)
+        return feats
+
 
 class LPIPS(nn.Module):
     def __init__(self):
@@ -228,9 +246,49 @@ class LPIPS(nn.Module):
         self.register_buffer("shift", torch.tensor([-.030, -.088, -.188]).view(1, 3, 1, 1), persistent=False)
         self.register_buffer("scale", torch.tensor([.458, .448, .450]).view(1, 3, 1, 1), persistent=False)
 
+    _VGG16_CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)     # torchvision vgg16().features indices of the convolutions
+
+    def load_lpips_weights(self, lin_sd: dict, vgg16_sd: dict | None = None) -> None:
+        """lin_sd: the `lpips` package's weights file (vgg.pth: `lin{k}.model.1.weight`, k = 0..4).  vgg16_sd: torchvision's vgg16 state
+        dict (`features.N.weight` / `.bias` for the 13 convolutions; `classifier.*` entries are ignored), mapped onto `net.slice{s}.N.*`.
+        Strict: a missing or an extra key raises, and so does a shape mismatch."""
+        want = {f"lin{k}.model.1.weight" for k in range(5)}
+        _same_keys(set(lin_sd), want, "lpips lin weights")
+        sd = dict(lin_sd)
+        if vgg16_sd is not None:
+            feats = {k: v for k, v in vgg16_sd.items() if not k.startswith("classifier.")}
+            _same_keys(set(feats), {f"features.{n}.{p}" for n in self._VGG16_CONVS for p in ("weight", "bias")}, "vgg16 features")
+            for k, v in feats.items():
+                n, param = int(k.split(".")[1]), k.split(".")[2]
+                sd[f"net.slice{1 + sum(n >= b for b in (4, 9, 16, 23))}.{n}.{param}"] = v
+        res = self.load_state_dict(sd, strict=vgg16_sd is not None)
+        assert not res.unexpected_keys and all(k.startswith("net.") for k in res.missing_keys), res
+
+    def _hip_ok(self, a: Tensor, b: Tensor) -> bool:
+        """device route: fp32 device images, a split-arithmetic mode, a ground-truth `b`, no active dropout and no trained lin weight"""
+        if not (a.is_cuda and b.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.dim() == 4 and a.shape == b.shape
+                and self.net.slice1[0].weight.is_cuda and self.net.slice1[0].weight.dtype == torch.float32):
+            return False
+        if vit_ops.LINEAR_MODE not in ("bf16x6", "bf16x3", "f16x3") or b.requires_grad:
+            return False
+        lins = [getattr(self, f"lin{k}").model for k in range(5)]
+        if any(m[0].training and m[0].p > 0 for m in lins):
+            return False
+        return not (torch.is_grad_enabled() and any(m[1].weight.requires_grad for m in lins))
+
     def forward(self, a: Tensor, b: Tensor, normalize: bool = False) -> Tensor:
         if normalize:                                                       # [0,1] -> [-1,1]
             a, b = 2 * a - 1, 2 * b - 1
+        if self._hip_ok(a, b):
+            with torch.no_grad():                                           # the target side saves nothing
+                fb = self.net.preacts((b - self.shift) / self.scale)
+            fa = self.net.preacts((a - self.shift) / self.scale)
+            ws = [getattr(self, f"lin{k}").model[1].weight for k in range(5)]
+            return vit_ops.lpips_tail(fa, fb, ws, relu_in=True).view(-1, 1, 1, 1)
+        return self._forward_expression(a, b)
+
+    def _forward_expression(self, a: Tensor, b: Tensor) -> Tensor:
+        """the plain expression (CPU, the f32 mode, a target that needs a gradient); a and b already in [-1, 1]"""
         fa, fb = self.net((a - self.shift) / self.scale), self.net((b - self.shift) / self.scale)
         total = 0
         for k, (x, y) in enumerate(zip(fa, fb)):
@@ -238,6 +296,11 @@ class LPIPS(nn.Module):
             y = y / (y.pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
             total = total + getattr(self, f"lin{k}")((x - y) ** 2).mean(dim=(2, 3), keepdim=True)
         return total                                                        # (N,1,1,1)
+
+
+def _same_keys(got: set, want: set, what: str) -> None:
+    if got != want:
+        raise KeyError(f"{what}: missing {sorted(want - got)}, unexpected {sorted(got - want)}")
 
 
 @dataclass

@@ -5,8 +5,9 @@ Mirrors `ModelWrapperStyle.test_step_align` (src/model/model_wrapper_style.py:39
 3-vectors `cam_rot_delta`, `cam_trans_delta` stay at zero, receive dL/d(theta, rho) from the decoder
 (`theta` / `rho` of the rasterizer), take an Adam step, and are folded into the camera as a LEFT
 multiplication of the world->camera matrix, T_w2c' = exp(tau) T_w2c, then reset to zero.
-Losses: the reference sums its configured losses (MSE + LPIPS); LPIPS weights are not available
-offline, so the default here is MSE and any callable loss can be passed.
+Losses: the reference sums its configured losses (MSE + LPIPS); the default here is MSE and any callable
+loss can be passed -- LPIPS included (`losses.LossLpips`, on the HIP kernels for device images; its learned
+weights load with `LPIPS.load_lpips_weights` when the files are available).
 """
 from __future__ import annotations
 

@@ -98,15 +98,21 @@ def make_lr_scheduler(optimizer, warm_up_steps: int, max_steps: int, lr: float):
 class TrainStep:
     """One optimisation step.  `losses`: modules called as loss(prediction, batch, gaussians, global_step) and summed
     (`:205-209`); default = MSE.  `identity_loss`: if given, a second encoder + decoder pass with style := context view 0
-    (`:211-229`).  `batch["style"]["image"]` is in [0,1] and mapped to [-1,1] for a stylized encoder (`:151-155`)."""
+    (`:211-229`).  `batch["style"]["image"]` is in [0,1] and mapped to [-1,1] for a stylized encoder (`:151-155`).
+    `extra_losses` (only with `losses=None`): modules of the same interface added on top of the default MSE, which stays inside
+    the composite kernels -- the reference's `/loss: [mse, lpips]` is `extra_losses=[LossLpips()]`; their image gradient enters
+    the same composite backward."""
 
     def __init__(self, encoder: nn.Module, decoder: nn.Module, lr: float = 2e-4, dist=None, bucket_bytes: int = 64 << 20,
                  clip: Optional[float] = 0.5, losses: Optional[Sequence[nn.Module]] = None,
                  identity_loss: Optional[nn.Module] = None, backbone_lr_multiplier: float = 0.1,
                  warm_up_steps: Optional[int] = None, max_steps: int = 100_000, force_collective: bool = False,
-                 dp_mode: Optional[str] = None):
+                 dp_mode: Optional[str] = None, extra_losses: Optional[Sequence[nn.Module]] = None):
         self.encoder, self.decoder, self.clip = encoder, decoder, clip
         self.losses, self.identity_loss = (list(losses) if losses is not None else None), identity_loss
+        if extra_losses and losses is not None:
+            raise ValueError("TrainStep: extra_losses are added to the default (fused) MSE; with `losses` list every loss there instead")
+        self.extra_losses = list(extra_losses or [])
         # identical replicas before anything else looks at the parameters (DDP semantics: rank 0's state wins)
         self.synced_bytes = broadcast_module_state(encoder, dist, force_collective=force_collective)
         new, pre, self.frozen_names = select_trainable(encoder)
@@ -140,6 +146,8 @@ class TrainStep:
         g, out = self._render(ctx, style, tgt, tgt["image"] if fuse else None)
         if self.losses is None:
             total = out.loss_mse if fuse else mse_loss(out.color, tgt["image"])     # LossMse
+            for fn in self.extra_losses:                                   # e.g. LPIPS: its image gradient joins the fused MSE's
+                total = total + fn(out, batch, g, self.global_step)
         else:
             total = sum(fn(out, batch, g, self.global_step) for fn in self.losses)
         if self.identity_loss is not None:

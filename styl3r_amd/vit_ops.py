@@ -38,10 +38,11 @@ from torch import Tensor, nn
 _PKG = Path(__file__).resolve().parent
 _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "lib" / os.environ.get("VIT_LIB_NAME", "libvit_hip.so")     # VIT_LIB_NAME: kernel-experiment builds (tools/ only); the product is libvit_hip.so
-_SOURCES = ["vit_rope.hip", "vit_attention.hip", "vit_attention_tail.hip", "vit_attention_bwd.hip", "vit_gemm.hip", "vit_attention_x6.hip", "vit_attention_bwd_x6.hip", "vit_gemm_x6.hip", "vit_gemm_sm.hip", "vit_gemm_x6r.hip", "vit_resample.hip", "vit_head_tail.hip", "vit_layernorm.hip", "vit_adapter.hip", "vit_optim.hip", "vit_api.hip"]
+_SOURCES = ["vit_rope.hip", "vit_attention.hip", "vit_attention_tail.hip", "vit_attention_bwd.hip", "vit_gemm.hip", "vit_attention_x6.hip", "vit_attention_bwd_x6.hip", "vit_gemm_x6.hip", "vit_gemm_sm.hip", "vit_gemm_x6r.hip", "vit_resample.hip", "vit_head_tail.hip", "vit_layernorm.hip", "vit_adapter.hip", "vit_optim.hip", "vit_lpips.hip", "vit_api.hip"]
 EXPORTS = ("vit_rope2d", "vit_attention_fwd", "vit_attention_set_arith", "vit_attention_arith", "vit_attention_bwd", "vit_linear_fwd", "vit_split_weight_bytes",
            "vit_split_weight", "vit_x6_set_products", "vit_x6_products", "vit_x6_set_operand_amax", "vit_x6_set_output_amax", "vit_amax", "vit_split_weight_block_bytes", "vit_split_weight_block", "vit_split_weight_pair", "vit_split_conv_weight_pair", "vit_split_weights_many", "vit_linear_x6_fwd", "vit_linear_sm_set", "vit_linear_sm_ok", "vit_linear_sm_grouped", "vit_layernorm_fwd_grouped", "vit_linear_x6r_fwd", "vit_linear_x6c_fwd", "vit_linear_x6c_workspace_bytes", "vit_linear_x6c_choose_splits", "vit_linear_x6_wgrad", "vit_linear_x6_wgrad_acc", "vit_conv_x6_fwd", "vit_conv_x6_wgrad", "vit_upsample2x_fwd", "vit_upsample2x_bwd", "vit_relu_dropout_fwd", "vit_relu_dropout_bwd", "vit_layernorm_scratch_bytes", "vit_layernorm_fwd", "vit_layernorm_bwd",
-           "vit_adapter_fwd", "vit_adapter_bwd", "vit_head_tail_fwd", "vit_head_tail_bwd", "vit_im2col7", "vit_im2col3_rows", "vit_upsample2x_add_relu_fwd", "vit_adamw_step", "vit_version", "vit_last_error")
+           "vit_adapter_fwd", "vit_adapter_bwd", "vit_head_tail_fwd", "vit_head_tail_bwd", "vit_im2col7", "vit_im2col3_rows", "vit_upsample2x_add_relu_fwd", "vit_adamw_step",
+           "vit_lpips_scratch_bytes", "vit_lpips_stats_bytes", "vit_lpips_fwd", "vit_lpips_bwd", "vit_maxpool2x2_fwd", "vit_maxpool2x2_bwd", "vit_version", "vit_last_error")
 ERRORS = {-1: "VIT_EINVAL", -3: "VIT_ELAUNCH"}
 _lib = None
 
@@ -107,6 +108,10 @@ class VitAdapterArgs(C.Structure):
                 ("par_channels", C.c_int32), ("opacity_exponent", C.c_float),
                 ("pts0", C.c_void_p), ("ptsr", C.c_void_p), ("par0", C.c_void_p), ("parr", C.c_void_p), ("app", C.c_void_p),
                 ("sh_mask", C.c_void_p)]
+
+
+class VitLpipsTap(C.Structure):
+    _fields_ = [("fa", C.c_void_p), ("fb", C.c_void_p), ("w", C.c_void_p), ("dfa", C.c_void_p), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32)]
 
 
 class VitAttnArgs(C.Structure):
@@ -222,6 +227,19 @@ def load() -> C.CDLL:
     lib.vit_im2col3_rows.restype = C.c_int
     lib.vit_upsample2x_add_relu_fwd.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]
     lib.vit_upsample2x_add_relu_fwd.restype = C.c_int
+    tp = C.POINTER(VitLpipsTap)
+    lib.vit_lpips_scratch_bytes.argtypes = [tp, C.c_int, C.c_int]
+    lib.vit_lpips_scratch_bytes.restype = C.c_size_t
+    lib.vit_lpips_stats_bytes.argtypes = [tp, C.c_int, C.c_int]
+    lib.vit_lpips_stats_bytes.restype = C.c_size_t
+    lib.vit_lpips_fwd.argtypes = [tp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.vit_lpips_fwd.restype = C.c_int
+    lib.vit_lpips_bwd.argtypes = [tp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.vit_lpips_bwd.restype = C.c_int
+    lib.vit_maxpool2x2_fwd.argtypes = [vp, vp, C.c_int64, C.c_int, C.c_int, vp]
+    lib.vit_maxpool2x2_fwd.restype = C.c_int
+    lib.vit_maxpool2x2_bwd.argtypes = [vp, vp, vp, C.c_int64, C.c_int, C.c_int, vp]
+    lib.vit_maxpool2x2_bwd.restype = C.c_int
     lib.vit_version.restype = C.c_char_p
     lib.vit_last_error.restype = C.c_char_p
     _lib = lib
@@ -991,7 +1009,8 @@ CALLS = {"linear_x6r": 0, "conv_wgrad_via_linear": 0, "head_tail": 0, "input_mer
          "layernorm_framework": 0, "adapter_hip": 0,
          # library / framework routes taken ON DEVICE TENSORS (layers the hand-written kernels do not cover): the end-to-end tests assert that every one of them stays at zero
          "library_conv_fwd": 0, "library_conv_bwd": 0, "framework_upsample": 0, "framework_dropout": 0, "framework_linear": 0,
-         "input_merger_library": 0,
+         "input_merger_library": 0, "framework_maxpool": 0,
+         "lpips_hip_fwd": 0, "lpips_hip_bwd": 0, "maxpool_hip_fwd": 0, "maxpool_hip_bwd": 0,
          "amax_pass": 0, "amax_published": 0, "split_many_images": 0, "split_plan_reused": 0, "split_pair": 0}     # f16x3: activation |max| words from a vit_amax pass / from the producing kernel's epilogue     # (the 7x7 input merger on the library: only when the IMAGE needs a gradient, i.e. in parity tests)
 LIBRARY_ROUTES = ("library_conv_fwd", "library_conv_bwd", "framework_upsample", "framework_dropout", "layernorm_framework")
 
@@ -1164,6 +1183,112 @@ def upsample2x(x: Tensor) -> Tensor:
     if x.is_cuda:
         CALLS["framework_upsample"] += 1
     return torch.nn.functional.interpolate(x, scale_factor=2, mode="bilinear", align_corners=True)
+
+
+class _MaxPool2x2(torch.autograd.Function):
+    """nn.MaxPool2d(2, 2) on vit_maxpool2x2_fwd / _bwd: the backward recomputes the argmax from the saved input (no index tensor)"""
+
+    @staticmethod
+    def forward(ctx, x):
+        B, Cc, H, W = x.shape
+        x = _aligned(x)
+        out = torch.empty((B, Cc, H // 2, W // 2), dtype=torch.float32, device=x.device)
+        CALLS["maxpool_hip_fwd"] += 1
+        _check(load().vit_maxpool2x2_fwd(x.data_ptr(), out.data_ptr(), B * Cc, H, W, _stream(x.device)), "vit_maxpool2x2_fwd")
+        ctx.save_for_backward(x)
+        if _f16():          # every output is one of the inputs: |max| of the input bounds |max| of the output (a valid f16x3 scale)
+            w = _known_amax(x)
+            if w is not None:
+                _publish(out, w)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (x,) = ctx.saved_tensors
+        B, Cc, H, W = x.shape
+        g = g.contiguous().float()
+        din = torch.empty_like(x)
+        CALLS["maxpool_hip_bwd"] += 1
+        _check(load().vit_maxpool2x2_bwd(x.data_ptr(), g.data_ptr(), din.data_ptr(), B * Cc, H, W, _stream(g.device)), "vit_maxpool2x2_bwd")
+        return din
+
+
+def _aligned(x: Tensor) -> Tensor:
+    """contiguous fp32 with a 16-byte aligned base (a view at an odd offset is copied)"""
+    x = x.contiguous().float()
+    return x if x.data_ptr() % 16 == 0 else x.clone()
+
+
+def maxpool2x2(x: Tensor) -> Tensor:
+    """F.max_pool2d(x, 2, 2); device fp32 NCHW maps with even H and W take vit_maxpool2x2_fwd / _bwd, anything else the framework's
+    kernels.  Commutes with ReLU (max(relu(x)) = relu(max(x)), the mask of the ReLU follows at the argmax): LPIPS's VGG pools the
+    pre-activations."""
+    if x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[-1] % 2 == 0 and x.shape[-2] % 2 == 0 and x.numel() > 0:
+        return _MaxPool2x2.apply(x)
+    if x.is_cuda:
+        CALLS["framework_maxpool"] += 1
+    return torch.nn.functional.max_pool2d(x, 2, 2)
+
+
+def _lpips_table(fa, fb, ws, dfa=None):
+    taps = (VitLpipsTap * len(fa))()
+    for k, (a, b, w) in enumerate(zip(fa, fb, ws)):
+        taps[k] = VitLpipsTap(a.data_ptr(), b.data_ptr(), w.data_ptr(), dfa[k].data_ptr() if dfa is not None else None,
+                              a.shape[1], a.shape[2], a.shape[3])
+    return taps
+
+
+class _LpipsTail(torch.autograd.Function):
+    """dist (N,) = sum_k mean_hw sum_c w_k[c] (a^ - b^)^2 over the five taps (losses.LPIPS.forward's tail) on vit_lpips_fwd; the
+    backward is one vit_lpips_bwd for every tap.  The target taps get no gradient (ground truth).  Saved for the backward: the taps
+    and 16 B of per-pixel statistics (vit_lpips_stats_bytes)."""
+
+    @staticmethod
+    def forward(ctx, relu_in, *args):
+        n = len(args) // 3
+        fa = [_aligned(t) for t in args[:n]]
+        fb = [_aligned(t) for t in args[n:2 * n]]
+        ws = [t.detach().reshape(-1).contiguous().float() for t in args[2 * n:]]
+        N, dev = fa[0].shape[0], fa[0].device
+        for a, b, w in zip(fa, fb, ws):
+            assert a.shape == b.shape and a.shape[0] == N and w.numel() == a.shape[1], "lpips tail: matching taps, one weight per channel"
+        lib = load()
+        taps = _lpips_table(fa, fb, ws)
+        part = torch.empty(lib.vit_lpips_scratch_bytes(taps, n, N) // 4, dtype=torch.float32, device=dev)
+        want = any(ctx.needs_input_grad[1:1 + n])
+        stats = torch.empty(lib.vit_lpips_stats_bytes(taps, n, N) // 4, dtype=torch.float32, device=dev) if want else None
+        dist = torch.empty(N, dtype=torch.float32, device=dev)
+        CALLS["lpips_hip_fwd"] += 1
+        _check(lib.vit_lpips_fwd(taps, n, N, 1 if relu_in else 0, dist.data_ptr(), part.data_ptr(),
+                                 stats.data_ptr() if stats is not None else None, _stream(dev)), "vit_lpips_fwd")
+        if want:
+            ctx.save_for_backward(stats, *fa, *fb, *ws)
+        ctx.n, ctx.relu_in = n, bool(relu_in)
+        return dist
+
+    @staticmethod
+    def backward(ctx, g):
+        n = ctx.n
+        stats, *rest = ctx.saved_tensors
+        fa, fb, ws = rest[:n], rest[n:2 * n], rest[2 * n:]
+        g = g.contiguous().float()
+        dfa = [torch.empty_like(a) for a in fa]
+        taps = _lpips_table(fa, fb, ws, dfa)
+        CALLS["lpips_hip_bwd"] += 1
+        _check(load().vit_lpips_bwd(taps, n, fa[0].shape[0], 1 if ctx.relu_in else 0, g.data_ptr(), stats.data_ptr(), _stream(g.device)),
+               "vit_lpips_bwd")
+        return (None, *[d if ctx.needs_input_grad[1 + k] else None for k, d in enumerate(dfa)], *([None] * (2 * n)))
+
+
+def lpips_tail(fa, fb, weights, relu_in: bool = False) -> Tensor:
+    """(N,) LPIPS distances from the taps fa / fb (lists of (N, C_k, H_k, W_k) device fp32 tensors, up to five) and the 1x1 `lin`
+    weights (C_k elements each): sum_k mean_hw sum_c w_k[c] (a^_c - b^_c)^2 with a^ = a / (|a|_c + 1e-10) (relu_in: of max(a, 0)).
+    The target side `fb` is ground truth: it must not need a gradient (callers keep the torch expression for that case)."""
+    for t in (*fa, *fb):
+        _need_gpu(t, "lpips_tail")
+    assert not any(t.requires_grad for t in fb), "lpips_tail: the target taps are ground truth"
+    assert not (torch.is_grad_enabled() and any(w.requires_grad for w in weights)), "lpips_tail: the lin weights get no gradient"
+    return _LpipsTail.apply(bool(relu_in), *fa, *fb, *weights)
 
 
 class _ReluDropout(torch.autograd.Function):

@@ -24,7 +24,11 @@ ap.add_argument("--config", choices=["c3", "c4", "c5"], default="c3",
                 help="c3: NVS-pretrain, 2 ctx / 4 tgt views, MSE, everything trains.  c4: style stage, 4 ctx / 6 tgt views, "
                      "VGG style loss + identity pass (two encoder/decoder passes), backbone frozen (random-init VGG: no weights here).  "
                      "c5: stress shapes, 4 ctx views 512x512 -> 1 048 576 Gaussians/scene, sh_degree 4, 4 tgt views 512x512, MSE, all train")
+ap.add_argument("--extra-losses", choices=["lpips"], default=None,
+                help="lpips: also time the step with the reference's `/loss: [mse, lpips]` (TrainStep extra_losses=[LossLpips()], LPIPS-VGG on the "
+                     "HIP route, random-init weights), in the same process right after the MSE-only step; reported under `with_lpips`")
 args = ap.parse_args()
+assert not (args.extra_losses and args.config == "c4"), "--extra-losses: the c4 step lists its own losses (LossStyle + identity), not the default MSE"
 if args.linear_mode:
     from styl3r_amd import vit_ops as _vo
     _vo.LINEAR_MODE = args.linear_mode
@@ -69,6 +73,21 @@ for _ in range(args.warmup):
     step(batch)
 assert rasterizer.LAST_STATS["pairs"] > rasterizer.LAST_STATS["gaussians_per_scene"], rasterizer.LAST_STATS
 dt = dist_utils.timed_steps(lambda: step(batch), args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)
+peak_mse = torch.cuda.max_memory_allocated(dev)
+with_lpips = None
+if args.extra_losses == "lpips":
+    from styl3r_amd import vit_ops
+    from styl3r_amd.losses import LossLpips
+    step.extra_losses = [LossLpips().to(dev)]                      # same step object: the same encoder, optimizer state and batch
+    torch.cuda.reset_peak_memory_stats(dev)
+    n0 = vit_ops.CALLS["lpips_hip_bwd"]
+    for _ in range(args.warmup):
+        step(batch)
+    assert vit_ops.CALLS["lpips_hip_bwd"] > n0, "LPIPS did not take the HIP route"
+    dt_l = dist_utils.timed_steps(lambda: step(batch), args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)
+    with_lpips = {"losses": "[mse, lpips] (mse fused in the composite kernels, LPIPS-VGG weight 0.05)",
+                  "value": round(dist_utils.aggregate_throughput(b * v_tgt, args.steps, world, dt_l), 3), "unit": "views/s",
+                  "ms_per_step": round(1e3 * dt_l / args.steps, 2), "peak_mem_GB": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1)}
 if rank == 0:
     nparam = sum(p.numel() for p in enc.parameters())
     print(json.dumps({"metric": ("512x512" if c5 else "256x256") + " rendered views/sec, full train step (encoder+rasterizer fwd+bwd, AdamW, DP all-reduce)",
@@ -78,8 +97,8 @@ if rank == 0:
                       "value": round(dist_utils.aggregate_throughput(b * v_tgt, args.steps, world, dt), 3), "unit": "views/s",
                       "n_gpus": world, "ms_per_step": round(1e3 * dt / args.steps, 2), "scenes_per_gpu": b, "params": nparam,
                       "grad_bytes": 4 * sum(p.numel() for p in enc.parameters() if p.requires_grad),
-                      "buckets": len(step.reducer.buckets), "peak_mem_GB": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1),
+                      "buckets": len(step.reducer.buckets), "peak_mem_GB": round(peak_mse / 2**30, 1),
                       "dtype": "f32", "linear_arithmetic": __import__("styl3r_amd.vit_ops", fromlist=["x"]).LINEAR_MODE
-, "data": "synthetic, random-init weights"}))
+, "data": "synthetic, random-init weights", **({"with_lpips": with_lpips} if with_lpips else {})}))
 if dist is not None:
     dist.barrier(); dist.destroy_process_group()
