@@ -89,6 +89,10 @@ typedef struct GsrDims {
                                        2 = 2048.  Pick the smallest budget >= the longest per-tile list expected
                                        (status[GSR_ST_MAX_TILE] of an earlier call): more workgroups fit a CU.  Longer lists
                                        remain correct (sorted in global memory), only slower. */
+#define GSR_FLAG_SEG_SHIFT 10        /* bits 10-12: length L of the depth segments the composite backward cuts a tile's list into (one
+                                        work unit per segment, started from a checkpoint the composite forward stored at its end):
+                                        0 = by size (gsr_common.h seg_len), 1 = 64, 2 = 128, 3 = 192, 4 = 256, 5 = 384, 7 = one segment
+                                        per tile.  Part of the workspace layout: the forward and the backward of a call pass the same. */
 
 /* status words written by gsr_forward (device int32[GSR_STATUS_WORDS]) */
 #define GSR_STATUS_WORDS 8
@@ -96,6 +100,7 @@ typedef struct GsrDims {
 #define GSR_ST_OVERFLOW 1    /* 1 if R > pair_capacity: outputs are INVALID, re-run with a larger capacity */
 #define GSR_ST_MAX_TILE 2    /* longest per-tile list */
 #define GSR_ST_PAIRS_HI 3    /* high 32 bits of R */
+#define GSR_ST_UNITS 4       /* work units of the composite backward (GsrLayout.unit_order); 0 on overflow */
 
 /* Named offsets into the workspace (bytes), for the parity tests and the bench. */
 typedef struct GsrLayout {
@@ -118,6 +123,11 @@ typedef struct GsrLayout {
     size_t loss_ticket;  /* uint32[V + 1]   fused MSE: arrival counters of a view's tiles / of the views; zeroed by the tile scan */
     size_t loss_diff;    /* float[V*3*H*W]  fused MSE: image - target as the composite forward had it in registers; the backward scales it
                             to dL/dimage (one 12-byte read per pixel, as with a dL_dimage from outside) */
+    size_t final_C;      /* float4[V*H*W]   (r, g, b, depth) accumulated by the composite forward, background not added; written for tiles
+                            of more than one depth segment (the backward's segments start from final_C minus a checkpoint) */
+    size_t ckpt;         /* checkpoint slots of 256 pixels, 5 KiB each: float4 (T, r, g, b prefix)[4 quadrants][64 lanes], then float depth
+                            prefix[4][64].  Tile t's boundary m L (m = 1, 2, ...) is slot tile_offset[t] / L + m - 1: at most cap / L slots */
+    size_t unit_order;   /* uint32[2][units] (view*T + tile, depth segment) work units of the composite backward, longest first */
     size_t total;        /* total bytes */
 } GsrLayout;
 

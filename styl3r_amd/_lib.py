@@ -91,7 +91,8 @@ class GsrDims(C.Structure):
 
 class GsrLayout(C.Structure):
     _fields_ = [(n, C.c_size_t) for n in ("records", "tile_count", "tile_offset", "tile_cursor", "pairs", "point_list",
-                                          "final_T", "n_contrib", "grad_rec", "status", "tile_order", "pairs_alt", "loss_partial", "loss_ticket", "loss_diff", "total")]
+                                          "final_T", "n_contrib", "grad_rec", "status", "tile_order", "pairs_alt", "loss_partial", "loss_ticket", "loss_diff", "final_C", "ckpt", "unit_order",
+                                          "total")]
 
 
 class GsrFused(C.Structure):
@@ -109,7 +110,9 @@ GSR_FLAG_BIN_BALLOT = 32
 GSR_ID_MASK = 0x0FFFFFFF
 GSR_QUAD_SHIFT = 28
 GSR_FLAG_SORT_KEYS_SHIFT = 8
+GSR_FLAG_SEG_SHIFT = 10      # 1..5: depth segments of 64 / 128 / 192 / 256 / 384 entries, 7: one per tile, 0: by size
 GSR_STATUS_WORDS = 8
+GSR_ST_UNITS = 4
 GSR_VIEW_FLOATS = 64
 GSR_N_STAGES = 7
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")

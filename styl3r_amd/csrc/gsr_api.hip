@@ -257,6 +257,6 @@ __attribute__((visibility("default"))) int gsr_profile_set_stages(GsrProfile *p,
     return GSR_OK;
 }
 
-__attribute__((visibility("default"))) const char *gsr_version(void) { return "gsr-hip gfx950 0.6.0"; }
+__attribute__((visibility("default"))) const char *gsr_version(void) { return "gsr-hip gfx950 0.7.0"; }
 
 }  // extern "C"

@@ -1,8 +1,10 @@
 // gsr_backward.hip -- backward pipeline of the gfx950 rasterizer.
 //
-//   K6 composite_bwd    same tiling as the forward (one wavefront per tile, 4 pixels per
-//                       lane); the tile's sorted id list is walked back-to-front from the
-//                       tile's deepest contributor, 64 entries at a time: each lane gathers ONE
+//   K6 composite_bwd    same tiling as the forward (one wavefront per work unit = (tile, depth
+//                       segment of L list entries), 4 pixels per lane; units longest first);
+//                       the segment is walked back-to-front -- the deepest one from the tile's
+//                       deepest contributor, the others from the forward's checkpoint at their
+//                       end -- 64 entries at a time: each lane gathers ONE
 //                       entry's 48-byte record into a wave-private LDS slot (the quadrant mask
 //                       the forward left in the top bits of the list word rides along), then the
 //                       wave evaluates the batch from LDS broadcasts as straight-line code under
@@ -41,10 +43,12 @@ __global__ void __launch_bounds__(64) k_composite_bwd(GsrDims d, const GsrView *
                                                      bool mse, float mse_weight, const float *__restrict__ mse_grad_loss)
 {
     if (ws.status[GSR_ST_OVERFLOW]) return;
+    if (blockIdx.x >= (uint32_t)ws.status[GSR_ST_UNITS]) return;     // the grid is unit_capacity(): units beyond this launch's count
     __shared__ float4 s_q[64 * 3];
 
     const int gx = tiles_x(d.W), T = gx * tiles_y(d.H);
-    const uint32_t tv = ws.tile_order[blockIdx.y * gridDim.x + blockIdx.x];   // longest lists are launched first
+    const uint2 unit = ws.unit_order[blockIdx.x];    // (view*T + tile, depth segment), longest units are launched first
+    const uint32_t tv = unit.x;
     const int tile = (int)(tv % (uint32_t)T), v = (int)(tv / (uint32_t)T);
     const int lane = threadIdx.x;
     const int ox = (tile % gx) * TILE + (lane & 7), oy = (tile / gx) * TILE + (lane >> 3);
@@ -98,18 +102,42 @@ __global__ void __launch_bounds__(64) k_composite_bwd(GsrDims d, const GsrView *
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
     const int max_last = __builtin_amdgcn_readfirstlane((int)mx);   // wave-uniform (all-lanes maximum): batch / entry counters and the loop controls stay scalar
+    // this unit's depth segment [lo, top) of the list.  Nothing at or behind max_last composited anywhere in the tile: a segment that
+    // starts there has no work, and the one that contains it starts as the whole-list walk does (T = T_final, S as above).
+    const uint32_t seg = seg_len(d);
+    const int lo = (int)(unit.y * seg);
+    if (lo >= max_last) return;
+    int top = max_last;
+    if ((uint32_t)lo + seg < (uint32_t)max_last) {
+        // a segment in front of the deepest one starts from the forward's checkpoint at its end b = lo + L:  T = T_b and
+        // S = T_final (bg.g) + g.(C_final - C_b) (+ gd (D_final - D_b)), C_b the colour prefix of entries [0, b) -- what the walk
+        // from max_last arrives at, up to rounding.  Slot of boundary (unit.y + 1) L: tile_offset / L + unit.y.
+        top = lo + (int)seg;
+        const float *slot = ws.ckpt + (size_t)(start / seg + unit.y) * CKPT_SLOT_FLOATS;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int px = ox + (k & 1) * 8, py = oy + (k >> 1) * 8;
+            if (px < d.W && py < d.H) {
+                const float4 cb = reinterpret_cast<const float4 *>(slot)[k * 64 + lane];
+                const float4 cf = ws.final_C[v * P + (size_t)py * d.W + px];
+                Tr[k] = cb.x;
+                S[k] += g0[k] * (cf.x - cb.y) + g1[k] * (cf.y - cb.z) + g2[k] * (cf.z - cb.w);
+                if (DEPTH) S[k] += gd[k] * (cf.w - slot[4 * TILE_PIX + k * 64 + lane]);
+            }
+        }
+    }
     // DEPTH: ten sums, reduce10; depth-free: the nine live sums go through wave_reduce9 (GR_DEPTH's column of grad_rec keeps its zero)
     constexpr bool NINE = !DEPTH;
     int slot;                                   // the grad_rec column this lane publishes, -1: none
     if (NINE) { const int i9 = reduce9_slot(lane); slot = i9 < 0 ? -1 : (i9 < 3 ? i9 : i9 + 1); }      // v = s[0..2], s[4..9]
     else slot = reduce10_slot(lane);
 
-    // entries [0, max_last) of the sorted list, in batches from the back; slot l of a batch = entry hi-1-l.  Each lane
+    // entries [lo, top) of the sorted list, in batches from the back; slot l of a batch = entry hi-1-l.  Each lane
     // gathers one entry's record and parks it in LDS at the start of the batch (stage_entry): holding the NEXT batch in 12
     // registers across the whole evaluation (round 1) hid one ~1 us load per 64 entries (< 1 % of a batch's time) and cost
     // the kernel two waves per SIMD of occupancy.
-    for (int hi = max_last; hi > 0; hi -= 64) {
-        const int cnt = min(64, hi);
+    for (int hi = top; hi > lo; hi -= 64) {
+        const int cnt = min(64, hi - lo);
         // (single-wave workgroup: its LDS instructions execute in order, so a compiler barrier orders the staging stores against the
         //  previous batch's reads -- a __syncthreads would also wait, s_waitcnt vmcnt(0), for every gradient atomic still in flight)
         asm volatile("" ::: "memory");
@@ -493,8 +521,10 @@ int backward(const GsrDims &d, const GsrView *views, const float *means, const f
         const float *mg = fx ? fx->mse_grad_loss : nullptr;
         const float mw = fx ? fx->mse_weight : 0.f;
         const bool mse = mse_target != nullptr;
-        if (dL_ddepth) hipLaunchKernelGGL(k_composite_bwd<true>, dim3(T, V), dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
-        else hipLaunchKernelGGL(k_composite_bwd<false>, dim3(T, V), dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
+        // one wavefront per work unit; the unit count is on the device only (status word GSR_ST_UNITS): a grid of its bound, the rest exit
+        const dim3 grid((uint32_t)unit_capacity((size_t)V * T, cap, seg_len(d)));
+        if (dL_ddepth) hipLaunchKernelGGL(k_composite_bwd<true>, grid, dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
+        else hipLaunchKernelGGL(k_composite_bwd<false>, grid, dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
     }
     tm.end(GSR_STAGE_COMPOSITE_BWD); tm.begin(GSR_STAGE_PREPROCESS_BWD);
     const dim3 gG((d.G + 255) / 256, d.B);

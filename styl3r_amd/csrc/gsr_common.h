@@ -48,6 +48,9 @@ struct Ptrs {             // carved workspace
     uint32_t *n_contrib;
     float *grad_rec;
     int32_t *status;
+    float4 *final_C;        // (r, g, b, depth) the composite forward accumulated, background not added (tiles of > 1 segment)
+    float *ckpt;            // depth-segment checkpoints, CKPT_SLOT_FLOATS per (tile, boundary)
+    uint2 *unit_order;      // (view*T + tile, segment) work units of the composite backward, longest first
 };
 
 }  // namespace gsr
@@ -96,6 +99,31 @@ struct StageTimer {
 
 __host__ __device__ inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
 __host__ __device__ inline int tiles_y(int H) { return (H + TILE - 1) / TILE; }
+
+// ---- depth segments of the composite backward (include/gsr.h GSR_FLAG_SEG_SHIFT) ----
+// K6 runs one wavefront per (view, tile, segment): segment s of a tile covers list entries [s L, (s + 1) L).  The composite
+// forward stores a checkpoint of its 256 pixels at every boundary m L inside the list (T and the colour / depth prefixes),
+// from which the segment in front of the boundary starts.  L is a multiple of the 64-entry batch of both kernels.
+constexpr uint32_t SEG_ONE = 1u << 30;          // "one segment per tile": beyond any list (a tile lists a Gaussian at most once, G < 2^27)
+constexpr int CKPT_SLOT_FLOATS = 5 * TILE_PIX;  // float4 (T, r, g, b)[4 quadrants][64 lanes], then float depth[4][64]
+__host__ __device__ inline uint32_t seg_len(const GsrDims &d)
+{
+    switch ((d.flags >> GSR_FLAG_SEG_SHIFT) & 7) {
+        case 1: return 64u;
+        case 2: return 128u;
+        case 3: return 192u;
+        case 4: return 256u;
+        case 5: return 384u;
+        case 7: return SEG_ONE;
+        default: {   // by the size of the launch: fewer tiles, shorter segments (more waves for the chip's 1 024 SIMDs)
+            const long long vt = (long long)d.B * d.Vt * tiles_x(d.W) * tiles_y(d.H);
+            return vt >= 4096 ? 256u : (vt >= 1024 ? 128u : 64u);
+        }
+    }
+}
+// grid of K6: every non-empty tile has ceil(n / L) <= n / L + 1 units, so V*T + cap / L bounds the unit count of any launch that fits
+__host__ __device__ inline size_t unit_capacity(size_t VT, long long cap, uint32_t L) { return VT + (size_t)cap / L; }
+__host__ __device__ inline size_t ckpt_slots(long long cap, uint32_t L) { return (size_t)cap / L; }
 
 // ---- real SH tables (bands 0-3 = published 3DGS constants, band 4 = standard real SH) ----
 __device__ constexpr float SH_C0 = 0.28209479177387814f;

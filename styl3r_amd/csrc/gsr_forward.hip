@@ -182,12 +182,15 @@ constexpr int SCAN_PER_MAX = 16;
 
 // `rearm`: the counters are the caller's persistent ones (GsrFused.tile_count): leave them zero for the next forward.
 // `nticket`: fused-MSE arrival counters of this workspace to zero (0 = none).
-__global__ void __launch_bounds__(1024) k_scan_tiles(int n, long long capacity, Ptrs ws, int32_t *__restrict__ status, int rearm, int nticket)
+// `seg`, `umax`: segment length and unit capacity of K6's work-unit table (seg_len, unit_capacity).
+__global__ void __launch_bounds__(1024) k_scan_tiles(int n, long long capacity, Ptrs ws, int32_t *__restrict__ status, int rearm, int nticket,
+                                                     uint32_t seg, uint32_t umax)
 {
     __shared__ unsigned long long s_wave[16];
     __shared__ unsigned long long s_carry;
     __shared__ uint32_t s_max[16];
     __shared__ uint32_t s_bin[256], s_shift;
+    __shared__ uint32_t s_ubin[256], s_ushift, s_ovf, s_units, s_full, s_fcur, s_fw[16];
     __shared__ uint32_t s_cnt[1024 * SCAN_PER_MAX];
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     uint32_t mx = 0;
@@ -259,7 +262,7 @@ __global__ void __launch_bounds__(1024) k_scan_tiles(int n, long long capacity, 
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
     if (lane == 0) s_max[wid] = mx;
-    if (tid < 256) s_bin[tid] = 0u;
+    if (tid < 256) { s_bin[tid] = 0u; s_ubin[tid] = 0u; }
     __syncthreads();
     if (tid == 0) {
         uint32_t m = 0;
@@ -268,25 +271,77 @@ __global__ void __launch_bounds__(1024) k_scan_tiles(int n, long long capacity, 
         ws.tile_offset[n] = (uint32_t)min(R, (unsigned long long)0xffffffffu);
         int ovf = (R > (unsigned long long)capacity || R > 0xffffffffull) ? 1 : 0;
         int32_t st[GSR_STATUS_WORDS] = {(int32_t)(R & 0xffffffffull), ovf, (int32_t)m, (int32_t)(R >> 32), 0, 0, 0, 0};
-        for (int k = 0; k < GSR_STATUS_WORDS; ++k) { status[k] = st[k]; ws.status[k] = st[k]; }
+        for (int k = 0; k < GSR_STATUS_WORDS; ++k) { status[k] = st[k]; ws.status[k] = st[k]; }   // (GSR_ST_UNITS: below, same thread)
         uint32_t sh = 0;                       // 256 length classes covering [0, m]
         while ((m >> sh) > 255u) ++sh;
         s_shift = sh;
+        const uint32_t um = min(m, seg);       // units are at most min(m, L) long
+        sh = 0;
+        while ((um >> sh) > 255u) ++sh;
+        s_ushift = sh;
+        s_ovf = (uint32_t)ovf;
+        s_full = 0u; s_fcur = 0u;
     }
     __syncthreads();
     // Launch order of the composite kernels: longest lists first (counting sort into 256 length classes), so the
     // workgroups that take longest start first and the tail of K5 / K6 is made of short tiles (LPT scheduling).
-    const uint32_t sh = s_shift;
+    // K6's work units: a tile of n entries is ceil(n / L) units, ceil(n / L) - 1 "full" ones of length L and the last one of the rest.
+    // The full units come first, in tile order at the positions an exclusive scan of their counts gives (round 7: one LDS counter for
+    // all of them serialised ~2 * 10^4 atomics on one address, 16 -> 82 us for this kernel at the headline); the last units follow,
+    // longest first by the same counting sort as the tiles.  (After an overflow there is no unit table: the unit count stays 0.)
+    const uint32_t sh = s_shift, ush = s_ushift;
+    const bool units = s_ovf == 0u;
+    auto ucls = [&](uint32_t len) { return 255u - min(len >> ush, 255u); };
+    auto nfull = [&](uint32_t cnt) { return cnt ? (cnt - 1u) / seg : 0u; };
+    uint32_t fbase = 0;                        // fast path: position of this thread's first full unit
+    if (units && fast) {                       // (uniform)
+        uint32_t fs = 0;
+#pragma unroll
+        for (int e = 0; e < SCAN_PER_MAX; ++e) if (e < per) fs += nfull(c[e]);
+        uint32_t x = fs;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) s_fw[wid] = x;
+        __syncthreads();
+        fbase = x - fs;
+        for (int w = 0; w < wid; ++w) fbase += s_fw[w];
+        if (tid == 1023) s_full = fbase + fs;
+    }
+    auto ucount = [&](uint32_t cnt) {
+        if (!units || cnt == 0u) return;
+        if (!fast && cnt > seg) atomicAdd(&s_full, nfull(cnt));
+        atomicAdd(&s_ubin[ucls(cnt - nfull(cnt) * seg)], 1u);
+    };
+    auto uplace = [&](uint32_t i, uint32_t cnt) {
+        if (!units || cnt == 0u) return;
+        const uint32_t nf = nfull(cnt);
+        if (nf) {
+            const uint32_t p = fast ? fbase : atomicAdd(&s_fcur, nf);
+            fbase += nf;
+            for (uint32_t s = 0; s < nf; ++s)
+                if (p + s < umax) ws.unit_order[p + s] = make_uint2(i, s);
+        }
+        const uint32_t p = s_full + atomicAdd(&s_ubin[ucls(cnt - nf * seg)], 1u);
+        if (p < umax) ws.unit_order[p] = make_uint2(i, nf);
+    };
     if (fast) {
 #pragma unroll
         for (int e = 0; e < SCAN_PER_MAX; ++e)
-            if (e < per && tid * per + e < n) atomicAdd(&s_bin[255u - min(c[e] >> sh, 255u)], 1u);
+            if (e < per && tid * per + e < n) { atomicAdd(&s_bin[255u - min(c[e] >> sh, 255u)], 1u); ucount(c[e]); }
     } else {
-        for (int i = tid; i < n; i += 1024) atomicAdd(&s_bin[255u - min(ws.tile_count[i] >> sh, 255u)], 1u);
+        for (int i = tid; i < n; i += 1024) {
+            const uint32_t cnt = ws.tile_count[i];
+            atomicAdd(&s_bin[255u - min(cnt >> sh, 255u)], 1u);
+            ucount(cnt);
+        }
     }
     __syncthreads();
-    if (tid < 64) {                            // exclusive scan of the 256 bins by one wavefront (4 bins per lane)
-        uint32_t b0 = s_bin[tid * 4], b1 = s_bin[tid * 4 + 1], b2 = s_bin[tid * 4 + 2], b3 = s_bin[tid * 4 + 3];
+    if (tid < 128) {                           // exclusive scans of the 256 tile bins (wave 0) and unit bins (wave 1), 4 bins per lane
+        uint32_t *bins = tid < 64 ? s_bin : s_ubin;
+        uint32_t b0 = bins[lane * 4], b1 = bins[lane * 4 + 1], b2 = bins[lane * 4 + 2], b3 = bins[lane * 4 + 3];
         uint32_t t4 = b0 + b1 + b2 + b3, x = t4;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -294,19 +349,26 @@ __global__ void __launch_bounds__(1024) k_scan_tiles(int n, long long capacity, 
             if (lane >= o) x += y;
         }
         uint32_t off = x - t4;
-        s_bin[tid * 4] = off; s_bin[tid * 4 + 1] = off + b0; s_bin[tid * 4 + 2] = off + b0 + b1; s_bin[tid * 4 + 3] = off + b0 + b1 + b2;
+        bins[lane * 4] = off; bins[lane * 4 + 1] = off + b0; bins[lane * 4 + 2] = off + b0 + b1; bins[lane * 4 + 3] = off + b0 + b1 + b2;
+        if (tid == 127) s_units = x;
     }
     __syncthreads();
+    if (tid == 0) { status[GSR_ST_UNITS] = (int32_t)(s_full + s_units); ws.status[GSR_ST_UNITS] = (int32_t)(s_full + s_units); }
     if (fast) {
 #pragma unroll
         for (int e = 0; e < SCAN_PER_MAX; ++e) {
             const int i = tid * per + e;
-            if (e < per && i < n) ws.tile_order[atomicAdd(&s_bin[255u - min(c[e] >> sh, 255u)], 1u)] = (uint32_t)i;
+            if (e < per && i < n) {
+                ws.tile_order[atomicAdd(&s_bin[255u - min(c[e] >> sh, 255u)], 1u)] = (uint32_t)i;
+                uplace((uint32_t)i, c[e]);
+            }
         }
     } else {
         for (int i = tid; i < n; i += 1024) {
-            const uint32_t pos = atomicAdd(&s_bin[255u - min(ws.tile_count[i] >> sh, 255u)], 1u);
+            const uint32_t cnt = ws.tile_count[i];
+            const uint32_t pos = atomicAdd(&s_bin[255u - min(cnt >> sh, 255u)], 1u);
             ws.tile_order[pos] = (uint32_t)i;
+            uplace((uint32_t)i, cnt);
             if (rearm) ws.tile_count[i] = 0u;      // its last read
         }
     }
@@ -721,6 +783,9 @@ __global__ void __launch_bounds__(64) k_composite_fwd(GsrDims d, const GsrView *
         last[k] = 0;
         dmask[k] = __builtin_amdgcn_ballot_w64(!inside[k]);
     }
+    // depth segments of the backward: the next boundary inside the list and its checkpoint slot (include/gsr.h GsrLayout.ckpt)
+    const uint32_t seg = seg_len(d);
+    uint32_t ck_next = seg, ck_slot = start / seg;
 
     for (int base = 0; base < n; base += 64) {
         const int cnt = __builtin_amdgcn_readfirstlane(min(64, n - base));     // (scalar loop control)
@@ -773,6 +838,17 @@ __global__ void __launch_bounds__(64) k_composite_fwd(GsrDims d, const GsrView *
                 if (touched_tot && lane == 0) atomicAdd(n_touched + (size_t)v * d.G + (__float_as_uint(b.w)), (int)touched_tot);
             }
         }
+        if ((uint32_t)(base + 64) == ck_next && ck_next < (uint32_t)n) {
+            // a segment boundary: T and the colour / depth prefixes of the 256 pixels after entries [0, base + 64) -- the state the
+            // backward's segment in front of it starts from.  (Pixels already finished store their final values.)
+            float *slot = ws.ckpt + (size_t)ck_slot * CKPT_SLOT_FLOATS;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                reinterpret_cast<float4 *>(slot)[k * 64 + lane] = make_float4(Tr[k], C0[k], C1[k], C2[k]);
+                slot[4 * TILE_PIX + k * 64 + lane] = D[k];
+            }
+            ck_next += seg; ++ck_slot;
+        }
         if ((dmask[0] & dmask[1] & dmask[2] & dmask[3]) == ~0ull) break;
     }
 
@@ -791,6 +867,7 @@ __global__ void __launch_bounds__(64) k_composite_fwd(GsrDims d, const GsrView *
         image[(v * 3 + 2) * P + pix] = r2;
         out_depth[v * P + pix] = D[k];
         out_opacity[v * P + pix] = O[k];
+        if ((uint32_t)n > seg) ws.final_C[v * P + pix] = make_float4(C0[k], C1[k], C2[k], D[k]);   // (wave-uniform) the segments' end point
         if (mse_target) {       // (wave-uniform)
             const float e0 = r0 - mse_target[(v * 3 + 0) * P + pix], e1 = r1 - mse_target[(v * 3 + 1) * P + pix],
                         e2 = r2 - mse_target[(v * 3 + 2) * P + pix];
@@ -857,6 +934,10 @@ int layout(const GsrDims &d, long long cap, GsrLayout &L)
     L.loss_partial = take((V * T + V) * 4);
     L.loss_ticket = take((V + 1) * 4);
     L.loss_diff = take(V * 3 * P * 4);
+    const uint32_t seg = seg_len(d);
+    L.final_C = take(seg == SEG_ONE ? 0 : V * P * 16);
+    L.ckpt = take(ckpt_slots(cap, seg) * CKPT_SLOT_FLOATS * 4);
+    L.unit_order = take(unit_capacity(V * T, cap, seg) * 8);
     L.total = off;
     return GSR_OK;
 }
@@ -880,6 +961,9 @@ Ptrs carve(void *base, const GsrLayout &L)
     w.loss_partial = reinterpret_cast<float *>(p + L.loss_partial);
     w.loss_ticket = reinterpret_cast<uint32_t *>(p + L.loss_ticket);
     w.loss_diff = reinterpret_cast<float *>(p + L.loss_diff);
+    w.final_C = reinterpret_cast<float4 *>(p + L.final_C);
+    w.ckpt = reinterpret_cast<float *>(p + L.ckpt);
+    w.unit_order = reinterpret_cast<uint2 *>(p + L.unit_order);
     return w;
 }
 
@@ -926,7 +1010,11 @@ int forward(const GsrDims &d, const GsrView *views, const float *means, const fl
     }
 #undef GSR_LAUNCH_K1
     tm.end(GSR_STAGE_PREPROCESS); tm.begin(GSR_STAGE_SCAN);
-    hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, stream, V * T, cap, ws, status, persistent_counters ? 1 : 0, mse_target ? V + 1 : 0);
+    {
+        const uint32_t seg = seg_len(d);
+        hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, stream, V * T, cap, ws, status, persistent_counters ? 1 : 0, mse_target ? V + 1 : 0,
+                           seg, (uint32_t)unit_capacity((size_t)V * T, cap, seg));
+    }
     tm.end(GSR_STAGE_SCAN);
     if (bin) return launch_status();  // status is final here: the host can size / retry before the heavy stages
 render_phase:
