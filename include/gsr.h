@@ -225,6 +225,31 @@ int gsr_mse_backward(const float *pred, const float *target, const float *grad_l
                      float *grad_pred, void *stream);
 
 /*
+ * Image scores of the test step (src/evaluation/metrics.py:11-52) for N image pairs (N,C,H,W), device fp32, contiguous:
+ *   ssim[n] = mean over c of skimage structural_similarity(gt[n], pred[n], win_size=11, gaussian_weights=True, channel_axis=0,
+ *             data_range=1.0): Gaussian window sigma 1.5 / radius 5, sample covariance (x 121/120), C1 = 1e-4, C2 = 9e-4, the map
+ *             averaged over the (H-10) x (W-10) pixels left after skimage's crop of 5; inputs NOT clipped
+ *   mse[n]  = mean over C*H*W of (clip(gt,0,1) - clip(pred,0,1))^2, the argument of compute_psnr's -10 log10
+ * Two launches (one pass over both images, one fold of per-tile partials per image in index order): deterministic, and image n's
+ * scores do not depend on N.  H, W >= 11 (else GSR_EINVAL), C >= 1.  scratch: device memory of gsr_image_scores_scratch_bytes()
+ * (0 for invalid dimensions), no initialisation needed, not shared between concurrent calls.
+ */
+size_t gsr_image_scores_scratch_bytes(int64_t N, int C, int H, int W);
+int gsr_image_scores(const float *gt, const float *pred, int64_t N, int C, int H, int W, float *ssim, float *mse, void *scratch,
+                     void *stream);
+
+/*
+ * One pose step of test_step_align (src/model/model_wrapper_style.py:430-440) for n views, one launch:
+ *   Adam (torch.optim.Adam: beta1, beta2, eps, bias correction by `step` >= 1, two learning rates as its two parameter groups) on the
+ *   deltas (rot, trans), which are zero before every step; then c2w <- (SE3_exp(trans, rot) c2w^-1)^-1 (src/misc/cam_utils.py:67-137,
+ *   including the angle < 1e-5 series), the pose arithmetic in fp64.
+ *   c2w (n,4,4) in/out; m, v (n,6) Adam moments, (rot xyz, trans xyz) per view, zeroed by the caller before step 1;
+ *   grad_rot, grad_trans (n,3) dL/d(cam_rot_delta), dL/d(cam_trans_delta).  All device fp32, contiguous.
+ */
+int gsr_pose_adam_update(float *c2w, float *m, float *v, const float *grad_rot, const float *grad_trans, int64_t n, int step,
+                         float lr_rot, float lr_trans, float beta1, float beta2, float eps, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

@@ -1,0 +1,106 @@
+"""The test step: `ModelWrapperStyle.test_step` + `test_step_align` (src/model/model_wrapper_style.py:317-364, 391-461), the path every
+number the reference reports goes through -- encoder, target-pose alignment, final render, PSNR / SSIM / LPIPS.
+
+Deviations from the reference:
+  * b >= 1 scenes per call (the reference asserts b == 1).  The alignment objective is b x the batch loss: every loss averages over the
+    b scenes, so each scene's deltas then receive the gradient of their own b = 1 objective, and Adam is element-wise.  Scores are per
+    scene, shape (b,).
+  * The encoder runs under `no_grad` and its `requires_grad` flags are left alone (the reference sets them all False and switches the
+    encoder to eval mode in test_step_align; nothing trains here, and the caller owns the module's mode).
+  * LPIPS scores mean something only with learned weights: `scores["lpips_weights_loaded"]` says whether the module had them.
+Dataset loading, the evaluation index, saving images / videos / comparisons and logging stay with the caller.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Optional, Sequence
+
+import torch
+
+from . import metrics
+from .losses import LPIPS, LossMse
+
+ADAM_BETAS, ADAM_EPS = (0.9, 0.999), 1e-8       # torch.optim.Adam defaults (test_step_align builds Adam(opt_params) without options)
+
+
+@dataclass
+class TestCfg:
+    """the fields of `test` (config/main.yaml:55-63) that the test step reads"""
+    __test__ = False                             # (not a pytest test class)
+    align_pose: bool = True
+    pose_align_steps: int = 100
+    rot_opt_lr: float = 0.005
+    trans_opt_lr: float = 0.005
+    compute_scores: bool = True
+
+
+def align_target_poses(decoder, gaussians, batch: dict, losses: Sequence, cfg: TestCfg, global_step: int = 0):
+    """test_step_align (:391-447): `cfg.pose_align_steps` Adam steps on zero deltas (cam_rot_delta, cam_trans_delta) of every target view,
+    folded into the target c2w after each step.  Objective: sum of `loss.forward(output, batch, gaussians, global_step)` over `losses`; a
+    `LossMse` among them is computed inside the decoder's composite kernels (`mse_target`), the others are added on top.
+    Per step: one decoder forward + backward and one `gsr_pose_adam_update` launch; the per-step losses stay on the device until the end.
+    Returns (aligned extrinsics (b, v, 4, 4), per-step losses as floats)."""
+    from . import _lib
+    tgt = batch["target"]
+    image = tgt["image"]
+    b, v, _, h, w = image.shape
+    dev = image.device
+    if not losses:
+        raise ValueError("align_target_poses: the alignment objective needs at least one loss")
+    mse = next((fn for fn in losses if isinstance(fn, LossMse)), None)
+    if mse is not None and not (image.is_cuda and image.dtype == torch.float32 and not image.requires_grad):
+        raise ValueError("align_target_poses: the fused LossMse needs fp32 ground-truth target images on the GPU")
+    rest = [fn for fn in losses if fn is not mse]
+    fused = {} if mse is None else {"mse_target": image, "mse_weight": mse.cfg.weight}
+    n = b * v
+    rot = torch.zeros((b, v, 3), device=dev, requires_grad=True)
+    trans = torch.zeros((b, v, 3), device=dev, requires_grad=True)
+    extrinsics = tgt["extrinsics"].detach().float().contiguous().clone()          # updated in place by the kernel
+    exp_avg = torch.zeros((n, 6), device=dev)                                     # Adam state per view: (rot xyz, trans xyz)
+    exp_avg_sq = torch.zeros((n, 6), device=dev)
+    lib = _lib.load()
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    history = []
+    for step in range(1, cfg.pose_align_steps + 1):
+        with torch.enable_grad():
+            out = decoder.forward(gaussians, extrinsics, tgt["intrinsics"], tgt["near"], tgt["far"], (h, w),
+                                  cam_rot_delta=rot, cam_trans_delta=trans, **fused)
+            total = out.loss_mse if mse is not None else 0
+            for fn in rest:
+                total = total + fn.forward(out, batch, gaussians, global_step)
+            g_rot, g_trans = torch.autograd.grad(total * b if b > 1 else total, [rot, trans], allow_unused=True)
+        history.append(total.detach())
+        g_rot = torch.zeros_like(rot) if g_rot is None else g_rot.contiguous()
+        g_trans = torch.zeros_like(trans) if g_trans is None else g_trans.contiguous()
+        _lib.check(lib.gsr_pose_adam_update(extrinsics.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), g_rot.data_ptr(),
+                                            g_trans.data_ptr(), n, step, cfg.rot_opt_lr, cfg.trans_opt_lr, ADAM_BETAS[0], ADAM_BETAS[1],
+                                            ADAM_EPS, stream), "gsr_pose_adam_update")
+    return extrinsics, (torch.stack(history).tolist() if history else [])
+
+
+def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = TestCfg(), lpips: Optional[LPIPS] = None,
+              style: Optional[dict] = None, global_step: int = 0):
+    """test_step (:317-364) for b >= 1 scenes.  Returns (DecoderOutput of the (aligned) target views, scores): scores has the reference's
+    keys `psnr_ours`, `ssim_ours`, `lpips_ours` -- each the mean over a scene's target views, shape (b,) -- and `lpips_weights_loaded`;
+    empty when `cfg.compute_scores` is off."""
+    tgt = batch["target"]
+    b, v, _, h, w = tgt["image"].shape
+    style = style if style is not None else {"image": batch["context"]["image"][:, 0]}
+    with torch.no_grad():
+        gaussians = encoder(batch["context"], style, global_step)
+    extrinsics = align_target_poses(decoder, gaussians, batch, losses, cfg, global_step)[0] if cfg.align_pose else tgt["extrinsics"]
+    with torch.no_grad():
+        output = decoder.forward(gaussians, extrinsics, tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
+    if not cfg.compute_scores:
+        return output, {}
+    gt, pred = tgt["image"].reshape(b * v, -1, h, w), output.color.reshape(b * v, -1, h, w)
+    module = lpips if lpips is not None else metrics.get_lpips(pred.device)
+    psnr, ssim = metrics.image_scores(gt, pred)
+    lp = metrics.compute_lpips(gt, pred, module)
+    per_scene = lambda t: t.reshape(b, v).mean(dim=1)
+    return output, {"lpips_ours": per_scene(lp), "ssim_ours": per_scene(ssim), "psnr_ours": per_scene(psnr),
+                    "lpips_weights_loaded": bool(getattr(module, "weights_loaded", False))}
+
+
+test_step.__test__ = False                       # (not a pytest test function where a test module imports it)

@@ -245,6 +245,8 @@ class LPIPS(nn.Module):
             setattr(self, f"lin{k}", _LpipsLin(c))
         self.register_buffer("shift", torch.tensor([-.030, -.088, -.188]).view(1, 3, 1, 1), persistent=False)
         self.register_buffer("scale", torch.tensor([.458, .448, .450]).view(1, 3, 1, 1), persistent=False)
+        # True once load_lpips_weights has loaded both the lin layers and the VGG16 features: until then the distance is meaningless
+        self.weights_loaded = False
 
     _VGG16_CONVS = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)     # torchvision vgg16().features indices of the convolutions
 
@@ -263,6 +265,7 @@ class LPIPS(nn.Module):
                 sd[f"net.slice{1 + sum(n >= b for b in (4, 9, 16, 23))}.{n}.{param}"] = v
         res = self.load_state_dict(sd, strict=vgg16_sd is not None)
         assert not res.unexpected_keys and all(k.startswith("net.") for k in res.missing_keys), res
+        self.weights_loaded = vgg16_sd is not None
 
     def _hip_ok(self, a: Tensor, b: Tensor) -> bool:
         """device route: fp32 device images, a split-arithmetic mode, a ground-truth `b`, no active dropout and no trained lin weight"""
