@@ -94,6 +94,9 @@ typedef struct GsrDims {
                                         0 = by size (gsr_common.h seg_len), 1 = 64, 2 = 128, 3 = 192, 4 = 256, 5 = 384, 7 = one segment
                                         per tile.  Part of the workspace layout: the forward and the backward of a call pass the same. */
 
+#define GSR_FLAG_STYLES_CHUNK_SHIFT 13 /* bits 13-15, gsr_forward_styles only: the most styles one composite launch shades, 2 .. 4 (0 = 4).
+                                        More styles are served by further composite launches over the same sorted lists. */
+
 /* status words written by gsr_forward (device int32[GSR_STATUS_WORDS]) */
 #define GSR_STATUS_WORDS 8
 #define GSR_ST_PAIRS 0       /* R: total (tile, Gaussian) pairs over all views (low 32 bits) */
@@ -200,6 +203,27 @@ int gsr_backward_fused(const GsrDims *dims, const GsrView *views, const float *m
                        const float *dL_dimage, const float *dL_ddepth, float *dL_dmeans, float *dL_dcov6,
                        float *dL_dopac, float *dL_dshs, float *dL_dmeans2D, float *dL_dtau, const GsrFused *fx,
                        void *stream);
+
+/*
+ * Multi-style forward (inference): S Gaussian sets that share means / covariances / opacities and differ only in colour, rendered
+ * through the same V views in one pass.  Geometry, binning, tile scan, scatter and the per-tile depth sort run ONCE (the kernels of
+ * gsr_forward); the composite walks every tile's list once per launch of up to 4 styles and accumulates all of their colours.
+ *   shs      HOST array of S device pointers, each (B,G,M,3) or, when M == 0, RGB (B,G,3)
+ *   extra    device memory of gsr_styles_extra_bytes(dims, S) bytes (0 for S == 1, then it may be NULL): the colours of styles 1..S-1,
+ *            16 bytes per (style, view, Gaussian) -- per (style, scene, Gaussian) at sh_degree 0 / M == 0, where the colour does not
+ *            depend on the view.  Style 0's colour lives in the workspace's splat records as in gsr_forward.
+ *   tile_count  optional persistent per-tile counters, as GsrFused.tile_count (NULL: the workspace's, zeroed by the call)
+ * Outputs: image (S,V,3,H,W); ONE depth (V,H,W), opacity (V,H,W), radii (V,G); status as gsr_forward.
+ * The workspace is the one of gsr_workspace_layout, unchanged, and is left as gsr_forward on style 0 leaves it (sorted lists with the
+ * quadrant-mask bits, final_T, n_contrib) except for what only a backward reads: there is NO backward for this call, and
+ * GSR_FLAG_NTOUCHED / GSR_FLAG_PREZERO_GRADS are rejected (GSR_EINVAL).  GSR_FLAG_PHASE_BIN / _RENDER work as in gsr_forward.
+ * S == 1 forwards to gsr_forward.
+ */
+size_t gsr_styles_extra_bytes(const GsrDims *dims, int32_t S);   /* 0 for invalid dims or S < 1 */
+int gsr_forward_styles(const GsrDims *dims, int32_t S, const GsrView *views, const float *means, const float *cov6,
+                       const float *opac, const float *const *shs, int64_t pair_capacity, void *workspace, size_t workspace_bytes,
+                       void *extra, size_t extra_bytes, uint32_t *tile_count, float *image, float *depth, float *opacity,
+                       int32_t *radii, int32_t *status, void *stream);
 
 /*
  * Camera set-up of `render_cuda` (cuda_splatting.py:65-88) for V views in ONE launch: the 1/near rescale

@@ -18,7 +18,7 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_metrics.hip"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_metrics.hip", "gsr_styles.hip"]
 _HEADERS = ["gsr_common.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
@@ -110,6 +110,7 @@ GSR_FLAG_BIN_BALLOT = 32
 GSR_ID_MASK = 0x0FFFFFFF
 GSR_QUAD_SHIFT = 28
 GSR_FLAG_SORT_KEYS_SHIFT = 8
+GSR_FLAG_STYLES_CHUNK_SHIFT = 13   # gsr_forward_styles: most styles per composite launch, 2..4 (0 = 4)
 GSR_FLAG_SEG_SHIFT = 10      # 1..5: depth segments of 64 / 128 / 192 / 256 / 384 entries, 7: one per tile, 0: by size
 GSR_STATUS_WORDS = 8
 GSR_ST_UNITS = 4
@@ -118,7 +119,7 @@ GSR_N_STAGES = 7
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_fused", "gsr_backward_fused", "gsr_version", "gsr_profile_create",
            "gsr_profile_destroy", "gsr_profile_read", "gsr_profile_set_stages", "gsr_last_error", "gsr_build_views", "gsr_mse_scratch_bytes",
-           "gsr_mse_forward", "gsr_mse_backward", "gsr_image_scores_scratch_bytes", "gsr_image_scores", "gsr_pose_adam_update")
+           "gsr_mse_forward", "gsr_mse_backward", "gsr_image_scores_scratch_bytes", "gsr_image_scores", "gsr_pose_adam_update", "gsr_forward_styles", "gsr_styles_extra_bytes")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -151,6 +152,10 @@ def load() -> C.CDLL:
     lib.gsr_forward_fused.restype = C.c_int
     lib.gsr_backward_fused.argtypes = [C.POINTER(GsrDims), vp, vp, vp, vp, i64, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(GsrFused), vp]
     lib.gsr_backward_fused.restype = C.c_int
+    lib.gsr_forward_styles.argtypes = [C.POINTER(GsrDims), C.c_int32, vp, vp, vp, vp, C.POINTER(vp), i64, vp, sz, vp, sz, vp, vp, vp, vp, vp, vp, vp]
+    lib.gsr_forward_styles.restype = C.c_int
+    lib.gsr_styles_extra_bytes.argtypes = [C.POINTER(GsrDims), C.c_int32]
+    lib.gsr_styles_extra_bytes.restype = C.c_size_t
     lib.gsr_version.restype = C.c_char_p
     lib.gsr_build_views.argtypes = [vp, vp, vp, vp, vp, C.c_int32, C.c_int32, vp, vp]
     lib.gsr_build_views.restype = C.c_int

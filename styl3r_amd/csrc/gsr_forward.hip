@@ -969,7 +969,8 @@ Ptrs carve(void *base, const GsrLayout &L)
 
 int forward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *opac,
             const float *shs, long long cap, void *workspace, size_t workspace_bytes, float *image, float *depth,
-            float *opacity, int32_t *radii, int32_t *n_touched, int32_t *status, const GsrFused *fx, hipStream_t stream)
+            float *opacity, int32_t *radii, int32_t *n_touched, int32_t *status, const GsrFused *fx, hipStream_t stream,
+            bool composite)
 {
     GsrLayout L;
     int rc = layout(d, cap, L);
@@ -1030,7 +1031,9 @@ render_phase:
         const uint32_t lds_keys = sel == 1 ? 1024u : (sel == 2 ? 2048u : SORT_LDS_KEYS);
         hipLaunchKernelGGL(k_tile_sort, dim3(T, V), dim3(256), lds_keys * 8, stream, d, ws, lds_keys);
     }
-    tm.end(GSR_STAGE_SORT); tm.begin(GSR_STAGE_COMPOSITE_FWD);
+    tm.end(GSR_STAGE_SORT);
+    if (!composite) return launch_status();   // gsr_forward_styles (gsr_styles.hip) shades the sorted lists itself
+    tm.begin(GSR_STAGE_COMPOSITE_FWD);
     {
         const float mse_weight = fx ? fx->mse_weight : 0.f;
         float *mse_loss = fx ? fx->mse_loss : nullptr;

@@ -21,7 +21,7 @@ import torch
 from torch import Tensor, nn
 
 from .camera import get_fov, get_projection_matrix
-from .rasterizer import RasterMse, pack_views, rasterize_views
+from .rasterizer import RasterMse, pack_views, rasterize_views, rasterize_views_styles
 
 DepthRenderingMode = Literal["depth", "disparity", "relative_disparity", "log"]
 
@@ -186,6 +186,36 @@ class DecoderSplattingHIP(nn.Module):
             cam_rot_delta=flat(cam_rot_delta) if cam_rot_delta is not None else None,
             cam_trans_delta=flat(cam_trans_delta) if cam_trans_delta is not None else None, mse=mse)
         return DecoderOutput(out[0].reshape(b, v, 3, h, w), out[1].reshape(b, v, h, w), out[2] if mse is not None else None)
+
+
+    def forward_styles(self, gaussians: Gaussians, harmonics_list, extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
+                       image_shape) -> DecoderOutput:
+        """Serving: S Gaussian sets over ONE geometry -- `gaussians.means / covariances / opacities` and the S harmonics tensors
+        (b,G,3,d_sh) of `harmonics_list` (`gaussians.harmonics` is not read) -- through the same cameras in one rasterizer pass.
+        Returns `DecoderOutput` with color (S,b,v,3,h,w) and the one depth (b,v,h,w) the sets share.  color[s] is what
+        `forward(Gaussians(means, covariances, harmonics_list[s], opacities), ...)` renders.  Forward-only: with autograd enabled
+        and an input that requires grad this raises -- `forward` is the differentiable path."""
+        harmonics_list = list(harmonics_list)
+        tensors = [gaussians.means, gaussians.covariances, gaussians.opacities, *harmonics_list]
+        if not all(t.is_cuda for t in tensors) or not extrinsics.is_cuda:
+            raise RuntimeError("forward_styles needs tensors on an MI355X (HIP) device; there is no CPU path")
+        if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+            raise RuntimeError("forward_styles is forward-only (inference): `forward` is the differentiable path, one Gaussian set per "
+                               "call; call forward_styles under torch.no_grad() or with detached inputs")
+        b, v = extrinsics.shape[:2]
+        flat = lambda t: t.reshape(b * v, *t.shape[2:])
+        h, w = image_shape
+        degree = isqrt(harmonics_list[0].shape[-1]) - 1
+        if self.torch_view_setup:
+            views = prepare_views(flat(extrinsics), flat(intrinsics), flat(near), flat(far), self._background_rows(b * v),
+                                  self.make_scale_invariant)
+        else:
+            views = build_views_hip(flat(extrinsics), flat(intrinsics), flat(near), flat(far), self._background_rows(b * v),
+                                    self.make_scale_invariant)
+        shs = [hm.detach().permute(0, 1, 3, 2).contiguous() for hm in harmonics_list]          # (b,g,n,3)  cuda_splatting.py:76
+        out = rasterize_views_styles(gaussians.means, gaussians.covariances, gaussians.opacities, shs, views, image_shape, v,
+                                     sh_degree=degree, use_sh=True)
+        return DecoderOutput(out.image.reshape(len(shs), b, v, 3, h, w), out.depth.reshape(b, v, h, w))
 
 
 def get_decoder(cfg: DecoderSplattingCUDACfg) -> DecoderSplattingHIP:

@@ -799,6 +799,18 @@ class UnifiedGaussianAdapter(nn.Module):
                                 rotations.broadcast_to((*scales.shape[:-1], 4)), sh, opacities)
 
 
+@dataclass
+class SceneState:
+    """What `encode_scene` keeps of a scene for `restyle`: everything of the encoder's forward that does not depend on the style image."""
+    images: Tensor         # context images (b,v,c,h,w): shapes, and the adapter's layout decisions
+    enc_feat: Tensor       # backbone encoder features (b,v,l,c) with the intrinsics token: the stylizer's content tokens
+    enc_pos: Tensor        # their positions (b,v,l,2)
+    heads: list            # outputs of head jobs 0, 1, 3, 4 of `_head_jobs` (mean / Gaussian-parameter heads of view 0 and of the other views)
+    global_step: int
+    shared: Optional[tuple] = None   # (means, covariances, opacities) of the first restyle: later ones return these same tensors
+
+
+
 # --------------------------------------------------------------------------- encoder
 class EncoderNoPoSplatMultiTokenStyle(nn.Module):
     def __init__(self, cfg: EncoderNoPoSplatTokenStyleCfg, trunk_params: Optional[dict] = None):
@@ -893,6 +905,54 @@ class EncoderNoPoSplatMultiTokenStyle(nn.Module):
             sty_feat = self.token_stylizer(style, enc_feat, enc_pos)
 
         return self._heads_and_adapter(images, dec_feat, sty_feat, global_step, visualization_dump, self._run_heads)
+
+    # ---- serving: one scene, many styles ---------------------------------------------------------------------------------------------
+    # The style image enters `forward` only through token_stylizer -> gaussian_appearance_head -> the harmonics; the backbone, both
+    # decoders and the mean / Gaussian-parameter heads -- so means, covariances and opacities -- depend on the context alone.
+    def encode_scene(self, context: dict, global_step: int = 0) -> SceneState:
+        """The style-independent part of `forward`: backbone encoder + decoders and head jobs 0, 1, 3, 4."""
+        if self.gs_params_head_type != "dpt_gs":
+            raise NotImplementedError(f"unexpected self.gs_params_head_type={self.gs_params_head_type!r}")
+        images = context["image"]
+        v = images.shape[1]
+        self.backbone.branch_streams = bool(self.head_streams)
+        enc_feat, enc_pos = self.backbone.encode(context)
+        dec_feat = self.backbone.decode_split(enc_feat, enc_pos)
+        with torch.autocast("cuda", enabled=False):
+            jobs = self._head_jobs(images, dec_feat, None)
+            heads = self._run_heads([jobs[0], jobs[1]] + ([jobs[3], jobs[4]] if v > 1 else []), images)
+        return SceneState(images, enc_feat, enc_pos, heads, global_step)
+
+    def restyle(self, state: SceneState, style: dict, visualization_dump: Optional[dict] = None):
+        """The style-dependent rest: token stylizer on the cached encoder features, appearance head, adapter.
+        `restyle(encode_scene(ctx), style)` is `forward(ctx, style)`.  style["image"] (n,3,hs,ws): n == b styles, one per scene, return
+        one `Gaussians`; n > 1 styles for a b == 1 scene return a LIST of n `Gaussians` whose means / covariances / opacities are the
+        same tensors (the content tokens are expanded, not recomputed) -- what `DecoderSplattingHIP.forward_styles` takes as it is.
+        Every restyle of one state returns the means / covariances / opacities tensors of the first."""
+        images = state.images
+        b, v = images.shape[:2]
+        n = style["image"].shape[0]
+        if n != b and b != 1:
+            raise ValueError(f"restyle: {n} style images for {b} scenes (several styles per scene need b == 1)")
+        feat, pos = state.enc_feat, state.enc_pos
+        if n != b:
+            feat, pos = feat.expand(n, *feat.shape[1:]), pos.expand(n, *pos.shape[1:])
+        sty_feat = self.token_stylizer(style, feat, pos)
+        with torch.autocast("cuda", enabled=False):
+            # (job 2 of `_head_jobs`: only its shapes come from the images; n styles are n * v samples of the appearance head)
+            like = images if n == b else images.expand(n, *images.shape[1:])
+            app = self._run_heads([self._head_jobs(like, None, sty_feat)[2]], images)[0]
+            pts_0, par_0 = state.heads[:2]
+            rest = state.heads[2:] if v > 1 else [None, None]
+            out = []
+            for i in range(n if n != b else 1):
+                app_i = app if n == b else app[i * v:(i + 1) * v]
+                dump = visualization_dump if i == 0 else None
+                g = self._adapter(images, [pts_0, par_0, app_i, *rest], state.global_step, dump)
+                if state.shared is None:
+                    state.shared = (g.means, g.covariances, g.opacities)
+                out.append(Gaussians(state.shared[0], state.shared[1], g.harmonics, state.shared[2]))
+        return out[0] if n == b else out
 
     def _opacity_exponent(self, global_step: int) -> float:
         x_op = self.cfg.opacity_mapping
@@ -1055,6 +1115,11 @@ class EncoderNoPoSplatMulti(EncoderNoPoSplatMultiTokenStyle):
         else:
             raise NotImplementedError(f"unexpected head_type={cfg.gs_params_head_type!r}")
 
+    def encode_scene(self, context: dict, global_step: int = 0):
+        raise NotImplementedError("encode_scene / restyle belong to the stylizing encoder `noposplat_multi_token_style`; this encoder takes no style")
+
+    restyle = encode_scene
+
     def forward(self, context: dict, global_step: int = 0, visualization_dump: Optional[dict] = None) -> Gaussians:
         b, v, _, h, w = context["image"].shape
         _, _, dec_feat, _, images = self.backbone(context)
@@ -1114,6 +1179,12 @@ class EncoderNoPoSplatTokenStyle(EncoderNoPoSplatMultiTokenStyle):
         self.downstream_head1 = head_factory("dpt", "pts3d", self.structure_builder)
         self.gaussian_structure_head = head_factory("dpt_gs_sh", "gs_params", self.structure_builder, out_nchan=self.raw_gs_dim - d_sh3)
         self.gaussian_appearance_head = head_factory("dpt_gs_sh", "gs_params", self.token_stylizer, out_nchan=d_sh3)
+
+    def encode_scene(self, context: dict, global_step: int = 0):
+        # (this encoder's heads read the structure builder's tokens, not the dual decoders': the split of the parent class does not apply unchanged)
+        raise NotImplementedError("encode_scene / restyle are implemented for `noposplat_multi_token_style` (every documented run uses it)")
+
+    restyle = encode_scene
 
     def forward(self, context: dict, style: dict, global_step: int = 0, visualization_dump: Optional[dict] = None) -> Gaussians:
         b, v, _, h, w = context["image"].shape

@@ -261,6 +261,106 @@ def rasterize_views(means: Tensor, cov6: Tensor, opacities: Tensor, colors: Tens
     return RasterOutput(*out)
 
 
+class StylesOutput(NamedTuple):
+    image: Tensor      # (S,V,3,H,W)
+    radii: Tensor      # (V,G) int32
+    depth: Tensor      # (V,H,W)
+    opacity: Tensor    # (V,H,W)
+
+
+# flags OR-ed into every multi-style call (tools/bench_restyle.py: styles per composite launch, _lib.GSR_FLAG_STYLES_CHUNK_SHIFT)
+STYLES_EXTRA_FLAGS = 0
+
+
+def rasterize_views_styles(means: Tensor, cov: Tensor, opacities: Tensor, colors_list, views: Tensor, image_hw,
+                           views_per_scene: int, sh_degree: int = 0, use_sh: bool = True) -> StylesOutput:
+    """S Gaussian sets that share means (B,G,3), cov (B,G,6) or (B,G,3,3) and opacities (B,G) and differ only in colour --
+    `colors_list`: S tensors, SH (B,G,M,3) or RGB (B,G,3) -- through the same views in ONE pass (include/gsr.h gsr_forward_styles):
+    geometry, binning and the per-tile sort run once, the composite accumulates every style's colour while it walks a tile's list.
+    Inference only: nothing here is differentiable (`rasterize_views` is), and inputs that require grad under autograd are refused."""
+    colors_list = list(colors_list)
+    S = len(colors_list)
+    if S < 1:
+        raise ValueError("rasterize_views_styles: at least one colour set")
+    tensors = [means, cov, opacities, *colors_list]
+    if not all(t.is_cuda for t in tensors) or not views.is_cuda:
+        raise RuntimeError("styl3r_amd rasterizer needs tensors on an MI355X (HIP) device; there is no CPU path")
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("rasterize_views_styles is forward-only: the differentiable path is `rasterize_views` / "
+                           "`DecoderSplattingHIP.forward`, one colour set per call (or run this one under torch.no_grad())")
+    lib = _lib.load()
+    f = lambda t: t.detach().contiguous().float()
+    means, cov6, opac, views = f(means), f(cov), f(opacities), f(views)
+    colors_list = [f(c) for c in colors_list]
+    H, W = int(image_hw[0]), int(image_hw[1])
+    Vt = int(views_per_scene)
+    B, G = means.shape[0], means.shape[1]
+    V = views.shape[0]
+    assert V == B * Vt, (V, B, Vt)
+    cov9 = cov6.dim() == 4
+    assert (cov6.shape == (B, G, 3, 3) if cov9 else cov6.shape == (B, G, 6)) and opac.shape[:2] == (B, G)
+    assert all(c.shape == colors_list[0].shape for c in colors_list), "every style's colours in the same layout"
+    M = colors_list[0].shape[2] if use_sh else 0
+    assert colors_list[0].shape == ((B, G, M, 3) if use_sh else (B, G, 3)), colors_list[0].shape
+    key = (B, Vt, G, H, W)
+    mt = _MAX_TILE_HINT.get(key, 4096)
+    sort_sel = 1 if mt <= 1024 else (2 if mt <= 2048 else 0)
+    flags = (_lib.GSR_FLAG_COV9 if cov9 else 0) | (sort_sel << _lib.GSR_FLAG_SORT_KEYS_SHIFT) | EXTRA_FLAGS | STYLES_EXTRA_FLAGS
+    dims = _lib.GsrDims(B, Vt, G, H, W, M, int(sh_degree) if use_sh else 0, flags, PROFILE.handle if PROFILE is not None else None)
+    dev = means.device
+    image = torch.empty((S, V, 3, H, W), dtype=torch.float32, device=dev)
+    depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    opacity = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+    radii = torch.empty((V, G), dtype=torch.int32, device=dev)
+    extra_bytes = int(lib.gsr_styles_extra_bytes(C.byref(dims), S))
+    extra = torch.empty(max(extra_bytes, 16), dtype=torch.uint8, device=dev)
+    shs = (C.c_void_p * S)(*[c.data_ptr() for c in colors_list])
+    stream_handle = torch.cuda.current_stream(dev).cuda_stream
+    stream = C.c_void_p(stream_handle)
+    cap = _CAP_HINT.get(key, max(4 * V * G, 1 << 16))
+    T = ((H + 15) // 16) * ((W + 15) // 16)
+    counters = _tile_counters(dev, stream_handle, V * T)
+    st, ev = _status_host(dev)
+    status = st if STATUS_DIRECT else torch.empty(_lib.GSR_STATUS_WORDS, dtype=torch.int32, device=dev)
+
+    # the two-phase forward of `_Rasterize.forward`: bin, record an event, enqueue the render phase optimistically, then read the pair count
+    def run(phase):
+        dims.flags = flags | phase
+        rc = lib.gsr_forward_styles(C.byref(dims), S, _ptr(views), _ptr(means), _ptr(cov6), _ptr(opac), shs, cap, _ptr(ws), L.total,
+                                    _ptr(extra), extra_bytes, _ptr(counters), _ptr(image), _ptr(depth), _ptr(opacity), _ptr(radii),
+                                    _ptr(status), stream)
+        dims.flags = flags
+        _lib.check(rc, "gsr_forward_styles")
+
+    try:
+        while True:
+            L = _lib.workspace_layout(dims, cap)
+            ws = torch.empty(L.total, dtype=torch.uint8, device=dev)
+            run(_lib.GSR_FLAG_PHASE_BIN)
+            if not STATUS_DIRECT:
+                st.copy_(status, non_blocking=True)
+            ev.record(torch.cuda.current_stream(dev))
+            run(_lib.GSR_FLAG_PHASE_RENDER)
+            while not ev.query():
+                pass
+            R = (int(st[3]) << 32) | (int(st[0]) & 0xFFFFFFFF)
+            if int(st[1]) == 0:
+                break
+            if R > 0xFFFFFFFF:
+                raise RuntimeError(f"gsr_forward_styles: {R} (tile, Gaussian) pairs exceed the 2^32 list limit")
+            cap = int(R * 1.25) + 1024
+    except BaseException:
+        _COUNTERS.pop((dev.index, stream_handle), None)     # the counters may be left half-counted: never reuse them
+        raise
+    st = st.clone()
+    _CAP_HINT[key] = max(_CAP_HINT.get(key, 0), min(int(R * 1.25) + 1024, 0xFFFFFFFF), 1 << 16)
+    _MAX_TILE_HINT[key] = max(_MAX_TILE_HINT.get(key, 0), int(int(st[2]) * 1.25))
+    LAST_STATS.update(pairs=R, views=V, gaussians_per_scene=G, longest_tile_list=int(st[2]))
+    if KEEP_DEBUG:
+        LAST_DEBUG.update(ws=ws, layout=L, dims=dims, cap=cap, num_pairs=R, status=st)
+    return StylesOutput(image, radii, depth, opacity)
+
+
 # ---------------------------------------------------------------------------
 # drop-in interface of `diff_gaussian_rasterization`
 # ---------------------------------------------------------------------------
