@@ -274,6 +274,46 @@ int gsr_pose_adam_update(float *c2w, float *m, float *v, const float *grad_rot, 
                          float lr_rot, float lr_trans, float beta1, float beta2, float eps, void *stream);
 
 /*
+ * Initial relative pose from predicted geometry, `get_pnp_pose` (src/misc/cam_utils.py:158-178) without the host round trip through
+ * cv2.solvePnPRansac: P independent problems in one call, all on `stream`, no host synchronisation, no float atomics; a problem's
+ * outputs are bit-identical whether it is solved alone or in a batch.  The contract is the geometry, not OpenCV's random stream.
+ *   pts3d (P,N,3), opacity (P,N): device fp32, N = H*W in row-major pixel order; point i is observed at pixel
+ *     (x, y) = (i % W + pixel_offset, i / W + pixel_offset)  (pixel_offset 0 = the reference's np.mgrid grid);
+ *   K (P,3,3): device fp32 pixel-unit intrinsics (fx, skew, cx / 0, fy, cy / 0, 0, 1); points with opacity > opacity_threshold take part;
+ *   `iterations` (1..4096) six-point hypotheses drawn with a counter-based generator keyed by (seed, hypothesis, draw), each
+ *   scored against every masked point (inlier: in front of the camera, reprojection distance <= reprojection_error pixels, integer
+ *   counts, ties to the lowest index), then a fixed number of Levenberg-Marquardt steps on the points within the bound.
+ *   c2w (P,4,4) fp32: inverse of the estimated world->camera; inlier_mask (P,N) uint8 or NULL: the points within the bound under it;
+ *   status (P,4) int32: masked points, inliers, index of the winning hypothesis (-1: none), code (0 ok, 1 fewer than 6 masked points,
+ *   2 no valid hypothesis).  A non-zero code leaves c2w = identity and an empty mask; it is never a fault.
+ *   scratch: device memory of gsr_pnp_ransac_scratch_bytes() (0 for invalid dimensions), no initialisation needed.
+ * GSR_EINVAL before any launch for null pointers, N != H*W, P < 1 or > 65535, iterations out of range, reprojection_error <= 0.
+ */
+size_t gsr_pnp_ransac_scratch_bytes(int64_t P, int H, int W, int iterations);
+int gsr_pnp_ransac(const float *pts3d, const float *opacity, const float *K, int64_t P, int H, int W, int64_t N, float opacity_threshold,
+                   float reprojection_error, int iterations, uint64_t seed, float pixel_offset, float *c2w, uint8_t *inlier_mask,
+                   int32_t *status, void *scratch, void *stream);
+
+/*
+ * The structure term of `ssim(X, Y, data_range=1, win_size=11, retrun_seprate=True)` (src/loss/loss_ssim.py:80-124) that the pose
+ * refinement adds to its objective (src/evaluation/pose_evaluator.py:128-133), for (N,C,H,W) device fp32 images, contiguous, H, W >= 11:
+ *   valid 11 x 11 filter with the 11 `window` taps (HOST pointer: _fspecial_gauss_1d(11, 1.5) as the caller's framework rounds it),
+ *   compensation 1, sigma^2 clamped below at finfo(float32).eps^2, |sigma12| capped at sqrt(sigma1^2 sigma2^2), C3 = C2 / 2,
+ *   structure_map = (sigma12 + C3) / (sigma1 sigma2 + C3) clamped above at 0.98;
+ *   structure[n] = mean over the (H-10) x (W-10) pixels and the C channels of image n (the reference's scalar is their mean over n).
+ * fwd: two launches (the pass + an ordered fold of per-tile float64 partials): deterministic, image n's value does not depend on N.
+ *   maps: NULL, or device fp32 [3][N*C*(H-10)*(W-10)] that receives the per-pixel adjoints d/d mu2, d/d E[y^2], d/d E[xy] (zero where
+ *   the 0.98 clamp is active) for the backward.  scratch: gsr_ssim_structure_scratch_bytes() of device memory, uninitialised.
+ * bwd: grad_pred[n] = grad_structure[n] * d structure[n] / d pred[n] -- the transposed filter of the three maps combined with the pixel's
+ *   own target / pred value; one launch, every element of grad_pred is written.  grad_structure: device fp32 [N].
+ */
+size_t gsr_ssim_structure_scratch_bytes(int64_t N, int C, int H, int W);
+int gsr_ssim_structure_fwd(const float *target, const float *pred, int64_t N, int C, int H, int W, const float *window, float *structure,
+                           float *maps, void *scratch, void *stream);
+int gsr_ssim_structure_bwd(const float *target, const float *pred, const float *maps, const float *grad_structure, int64_t N, int C, int H,
+                           int W, const float *window, float *grad_pred, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

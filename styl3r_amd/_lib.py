@@ -18,7 +18,7 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_metrics.hip", "gsr_styles.hip"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_metrics.hip", "gsr_styles.hip", "gsr_pose.hip"]
 _HEADERS = ["gsr_common.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
@@ -119,7 +119,8 @@ GSR_N_STAGES = 7
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_fused", "gsr_backward_fused", "gsr_version", "gsr_profile_create",
            "gsr_profile_destroy", "gsr_profile_read", "gsr_profile_set_stages", "gsr_last_error", "gsr_build_views", "gsr_mse_scratch_bytes",
-           "gsr_mse_forward", "gsr_mse_backward", "gsr_image_scores_scratch_bytes", "gsr_image_scores", "gsr_pose_adam_update", "gsr_forward_styles", "gsr_styles_extra_bytes")
+           "gsr_mse_forward", "gsr_mse_backward", "gsr_image_scores_scratch_bytes", "gsr_image_scores", "gsr_pose_adam_update", "gsr_forward_styles", "gsr_styles_extra_bytes",
+           "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_ransac", "gsr_ssim_structure_scratch_bytes", "gsr_ssim_structure_fwd", "gsr_ssim_structure_bwd")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -172,6 +173,16 @@ def load() -> C.CDLL:
     lib.gsr_image_scores.restype = C.c_int
     lib.gsr_pose_adam_update.argtypes = [vp, vp, vp, vp, vp, i64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp]
     lib.gsr_pose_adam_update.restype = C.c_int
+    lib.gsr_pnp_ransac_scratch_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.gsr_pnp_ransac_scratch_bytes.restype = C.c_size_t
+    lib.gsr_pnp_ransac.argtypes = [vp, vp, vp, i64, C.c_int, C.c_int, i64, C.c_float, C.c_float, C.c_int, C.c_uint64, C.c_float, vp, vp, vp, vp, vp]
+    lib.gsr_pnp_ransac.restype = C.c_int
+    lib.gsr_ssim_structure_scratch_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.gsr_ssim_structure_scratch_bytes.restype = C.c_size_t
+    lib.gsr_ssim_structure_fwd.argtypes = [vp, vp, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), vp, vp, vp, vp]
+    lib.gsr_ssim_structure_fwd.restype = C.c_int
+    lib.gsr_ssim_structure_bwd.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), vp, vp]
+    lib.gsr_ssim_structure_bwd.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

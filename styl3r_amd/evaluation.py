@@ -9,6 +9,9 @@ Deviations from the reference:
     encoder to eval mode in test_step_align; nothing trains here, and the caller owns the module's mode).
   * LPIPS scores mean something only with learned weights: `scores["lpips_weights_loaded"]` says whether the module had them.
 Dataset loading, the evaluation index, saving images / videos / comparisons and logging stay with the caller.
+
+`estimate_relative_pose` (below) is the reference's other evaluation, `PoseEvaluator.test_step` (src/evaluation/pose_evaluator.py:48-164): the
+pose of the context views relative to the first from a PnP-RANSAC initialisation and the same alignment loop with the SSIM-structure term added.
 """
 from __future__ import annotations
 
@@ -104,3 +107,69 @@ def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = Te
 
 
 test_step.__test__ = False                       # (not a pytest test function where a test module imports it)
+
+
+# ---- relative pose between the context views (src/evaluation/pose_evaluator.py:48-164) ------------------------------------------------
+@dataclass
+class PoseEvalCfg:
+    """what `PoseEvaluator.test_step` and `get_pnp_pose` hard-code, as fields"""
+    steps: int = 200
+    rot_lr: float = 0.005
+    trans_lr: float = 0.005
+    opacity_threshold: float = 0.3
+    pnp_iterations: int = 100
+    reprojection_error: float = 5.0
+    ssim_structure_weight: float = 1.0
+    seed: int = 0
+    pixel_offset: float = 0.0
+    context_normalized: bool = True             # context images are in [-1, 1]: the photometric target is image * 0.5 + 0.5
+
+
+def estimate_relative_pose(encoder, decoder, batch: dict, losses: Sequence, cfg: PoseEvalCfg = PoseEvalCfg(), style: Optional[dict] = None,
+                           init_pose: Optional[torch.Tensor] = None, global_step: int = 0) -> dict:
+    """The pose of every context view but the first, relative to the first, for b >= 1 scenes: the encoder once (no gradients, with a
+    visualization dump), `pose_align.pnp_pose` on each view's per-pixel means and opacities -- (b, v - 1) problems in one call -- unless
+    `init_pose` (b, v - 1, 4, 4) is given, then `cfg.steps` Adam steps of `align_target_poses` on the photometric objective
+    `losses + [LossSsimStructure]` against those context images.  Returns `pose_init`, `pose` (b, v - 1, 4, 4), `losses` (per step),
+    `pnp_status` (None with `init_pose`) and, when the context has ground-truth extrinsics, `e_t_ours`, `e_R_ours`,
+    `e_pose_ours = max(e_t, e_R)` in degrees, (b, v - 1), against the ground truth expressed in the first view's frame."""
+    from .losses import LossSsimStructure
+    from .pose_align import align_poses, pnp_pose
+    ctx = batch["context"]
+    b, v, _, h, w = ctx["image"].shape
+    if v < 2:
+        raise ValueError("estimate_relative_pose needs at least two context views")
+    style = style if style is not None else {"image": ctx["image"][:, 0]}
+    dump: dict = {}
+    with torch.no_grad():
+        gaussians = encoder(ctx, style, global_step, visualization_dump=dump)
+    status = None
+    if init_pose is None:
+        means, opac = dump["means"], dump["opacities"]
+        means = means.reshape(b, v, h, w, -1, 3)[:, 1:, :, :, 0]
+        opac = opac.reshape(b, v, h, w, -1)[:, 1:, :, :, 0]
+        pose_init, status = pnp_pose(means, opac, ctx["intrinsics"][:, 1:], (h, w), cfg.opacity_threshold, cfg.pnp_iterations,
+                                     cfg.reprojection_error, cfg.seed, cfg.pixel_offset)
+    else:
+        pose_init = init_pose.detach().float().reshape(b, v - 1, 4, 4)
+    image = ctx["image"][:, 1:].detach()
+    image = (image * 0.5 + 0.5 if cfg.context_normalized else image).contiguous()
+    target = {"image": image, "extrinsics": pose_init, "intrinsics": ctx["intrinsics"][:, 1:], "near": ctx["near"][:, 1:],
+              "far": ctx["far"][:, 1:]}
+    inner = {**batch, "target": target}
+    objective = list(losses) + [LossSsimStructure(cfg.ssim_structure_weight)]
+    if image.is_cuda:
+        pose, history = align_target_poses(decoder, gaussians, inner, objective,
+                                           TestCfg(pose_align_steps=cfg.steps, rot_opt_lr=cfg.rot_lr, trans_opt_lr=cfg.trans_lr), global_step)
+    else:                                       # host tensors: the framework loop with the same objective
+        from types import SimpleNamespace
+        fn = lambda color, _t: sum(f.forward(SimpleNamespace(color=color), inner, gaussians, global_step) for f in objective)
+        pose, history = align_poses(decoder, gaussians, image, pose_init, target["intrinsics"], target["near"], target["far"],
+                                    steps=cfg.steps, rot_lr=cfg.rot_lr, trans_lr=cfg.trans_lr, loss_fn=fn)
+    out = {"pose_init": pose_init, "pose": pose.detach(), "losses": history, "pnp_status": status}
+    if "extrinsics" in ctx:
+        E = ctx["extrinsics"].detach().float()
+        gt = torch.linalg.inv(E[:, :1]) @ E[:, 1:]
+        e_t, _, e_R = metrics.compute_pose_error(gt, out["pose"].to(gt.device))
+        out.update(e_t_ours=e_t, e_R_ours=e_R, e_pose_ours=torch.maximum(e_t, e_R))
+    return out

@@ -327,3 +327,129 @@ class LossLpips(nn.Module):
         b, v = image.shape[:2]
         loss = self.lpips(prediction.color.reshape(b * v, *image.shape[2:]), image.reshape(b * v, *image.shape[2:]), normalize=True)
         return self.cfg.weight * loss.mean()
+
+
+# ---------------------------------------------------------------------------
+# SSIM structure term of the pose refinement (src/evaluation/pose_evaluator.py:128-133):
+# `1 - structure` of src/loss/loss_ssim.py::ssim(target, pred, data_range=1.0, win_size=11, retrun_seprate=True).
+# ---------------------------------------------------------------------------
+SSIM_WIN, SSIM_SIGMA = 11, 1.5
+SSIM_C3 = 0.5 * (0.03 * 1.0) ** 2                 # C2 / 2, C2 = (K2 data_range)^2
+SSIM_EPS2 = torch.finfo(torch.float32).eps ** 2
+SSIM_STRUCTURE_MAX = 0.98
+
+
+def ssim_window() -> Tensor:
+    """`_fspecial_gauss_1d(11, 1.5)` (loss_ssim.py:12-26): formed and normalised in fp32, whatever the images' dtype"""
+    coords = torch.arange(SSIM_WIN, dtype=torch.float)
+    coords -= SSIM_WIN // 2
+    g = torch.exp(-(coords ** 2) / (2 * SSIM_SIGMA ** 2))
+    g /= g.sum()
+    return g
+
+
+def ssim_structure_map(target: Tensor, pred: Tensor, details: bool = False):
+    """the plain expression of loss_ssim.py:80-124 for (N, C, H, W): the structure map (N, C, H-10, W-10) after its 0.98 clamp.
+    `details`: also the quantities the branches switch on (raw map, |sigma12|, sqrt(sigma1^2 sigma2^2), the unclamped variances)."""
+    n, c, h, w = pred.shape
+    win = ssim_window().to(pred.device, pred.dtype)
+
+    def filt(t):                                   # valid, separable: height first, then width (gaussian_filter's order)
+        t = F.conv2d(t.reshape(n * c, 1, h, w), win.view(1, 1, -1, 1))
+        return F.conv2d(t, win.view(1, 1, 1, -1)).reshape(n, c, h - SSIM_WIN + 1, w - SSIM_WIN + 1)
+
+    x, y = target.to(pred.dtype), pred
+    mu1, mu2 = filt(x), filt(y)
+    raw1, raw2 = filt(x * x) - mu1.pow(2), filt(y * y) - mu2.pow(2)
+    raw12 = filt(x * y) - mu1 * mu2
+    s1, s2 = raw1.clamp(min=SSIM_EPS2), raw2.clamp(min=SSIM_EPS2)
+    cap = torch.sqrt(s1 * s2)
+    s12 = torch.sign(raw12) * torch.minimum(cap, raw12.abs())
+    raw = (s12 + SSIM_C3) / (torch.sqrt(s1) * torch.sqrt(s2) + SSIM_C3)
+    out = raw.clamp(max=SSIM_STRUCTURE_MAX)
+    return (out, raw, raw12.abs(), cap, raw1, raw2) if details else out
+
+
+def _structure_expression(target: Tensor, pred: Tensor) -> Tensor:
+    """per-image structure (N,): mean over the pixels, then the channels"""
+    return ssim_structure_map(target, pred).flatten(2).mean(-1).mean(1)
+
+
+_SSIM_WINDOW_C = None
+
+
+def _window_c():
+    import ctypes as C
+    global _SSIM_WINDOW_C
+    if _SSIM_WINDOW_C is None:
+        _SSIM_WINDOW_C = (C.c_float * SSIM_WIN)(*ssim_window().tolist())
+    return _SSIM_WINDOW_C
+
+
+class _SsimStructureHip(torch.autograd.Function):
+    """per-image structure (N,) on libgsr_hip.so (include/gsr.h gsr_ssim_structure_fwd / _bwd): the pass + an ordered fold; when `pred`
+    needs a gradient the pass also leaves the three adjoint maps the one-launch backward filters.  The target is ground truth."""
+
+    @staticmethod
+    def forward(ctx, pred, target):
+        import ctypes as C
+        from . import _lib
+        lib = _lib.load()
+        pred, target = pred.contiguous(), target.contiguous()
+        n, c, h, w = pred.shape
+        dev = pred.device
+        need = ctx.needs_input_grad[0]
+        maps = torch.empty((3, n * c * (h - SSIM_WIN + 1) * (w - SSIM_WIN + 1)), dtype=torch.float32, device=dev) if need else None
+        scratch = torch.empty(lib.gsr_ssim_structure_scratch_bytes(n, c, h, w), dtype=torch.uint8, device=dev)
+        out = torch.empty(n, dtype=torch.float32, device=dev)
+        _lib.check(lib.gsr_ssim_structure_fwd(target.data_ptr(), pred.data_ptr(), n, c, h, w, _window_c(), out.data_ptr(),
+                                              maps.data_ptr() if need else None, scratch.data_ptr(),
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "gsr_ssim_structure_fwd")
+        if need:
+            ctx.save_for_backward(pred, target, maps)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        import ctypes as C
+        from . import _lib
+        pred, target, maps = ctx.saved_tensors
+        n, c, h, w = pred.shape
+        grad = torch.empty_like(pred)
+        g = g.contiguous().float()
+        _lib.check(_lib.load().gsr_ssim_structure_bwd(target.data_ptr(), pred.data_ptr(), maps.data_ptr(), g.data_ptr(), n, c, h, w, _window_c(),
+                                                      grad.data_ptr(), C.c_void_p(torch.cuda.current_stream(pred.device).cuda_stream)),
+                   "gsr_ssim_structure_bwd")
+        return grad, None
+
+
+def ssim_structure_per_image(target: Tensor, pred: Tensor) -> Tensor:
+    """structure (N,) of (N, C, H, W) images, H, W >= 11; differentiable with respect to `pred`.  fp32 device tensors with a ground-truth
+    target go through the HIP kernels (and raise if libgsr_hip.so is missing); anything else is the plain torch expression."""
+    if pred.dim() != 4 or pred.shape != target.shape:
+        raise ValueError(f"ssim_structure takes two (N, C, H, W) tensors of one shape, got {tuple(target.shape)} and {tuple(pred.shape)}")
+    if min(pred.shape[-2:]) < SSIM_WIN:
+        raise ValueError("ssim_structure: the 11 x 11 window needs height and width >= 11")
+    if pred.is_cuda and target.is_cuda and pred.dtype == torch.float32 and target.dtype == torch.float32 and not target.requires_grad \
+            and pred.numel() > 0:
+        return _SsimStructureHip.apply(pred, target)
+    return _structure_expression(target, pred)
+
+
+def ssim_structure(target: Tensor, pred: Tensor) -> Tensor:
+    """the `structure` scalar of `ssim(target, pred, size_average=True, data_range=1.0, retrun_seprate=True, win_size=11)`"""
+    return ssim_structure_per_image(target, pred).mean()
+
+
+class LossSsimStructure(nn.Module):
+    """`(1 - structure) * weight` of the rendered views against `batch["target"]["image"]` (pose_evaluator.py:128-133), with the interface
+    of the other losses so that it drops into `evaluation.align_target_poses`"""
+
+    def __init__(self, weight: float = 1.0):
+        super().__init__()
+        self.weight = weight
+
+    def forward(self, prediction, batch, gaussians=None, global_step: int = 0) -> Tensor:
+        image = batch["target"]["image"]
+        b, v = image.shape[:2]
+        return self.weight * (1 - ssim_structure(image.reshape(b * v, *image.shape[2:]), prediction.color.reshape(b * v, *image.shape[2:])))

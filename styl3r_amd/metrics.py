@@ -9,6 +9,8 @@ SSIM is what the reference gets from `skimage.metrics.structural_similarity(gt, 
 data_range=1.0)`: the separable Gaussian window of sigma 1.5 and radius 5, sample covariance (x 121/120), C1 = 1e-4, C2 = 9e-4, the map
 averaged over the pixels left after skimage's crop of 5 from every edge and then over the channels; the inputs are not clipped.  Every
 kept pixel's window lies inside the image, so the valid filter of the interior is exact and skimage's boundary mode never enters.
+
+`compute_pose_error` (src/evaluation/metrics.py:87-99) and `pose_auc` (src/misc/cam_utils.py:181-193) are the relative-pose scores.
 """
 from __future__ import annotations
 
@@ -135,3 +137,34 @@ def compute_lpips(ground_truth: Tensor, predicted: Tensor, lpips: LPIPS | None =
     module = lpips if lpips is not None else get_lpips(predicted.device)
     return module.forward(ground_truth, predicted, normalize=True)[:, 0, 0, 0]
 
+
+
+# ---- relative camera pose (src/evaluation/metrics.py:70-99, src/misc/cam_utils.py:181-193) --------------------------------------------
+@torch.no_grad()
+def compute_pose_error(pose_gt: Tensor, pose_pred: Tensor):
+    """(error_t, error_t_scale, error_R) of camera-to-world poses (..., 4, 4): the angle between the translations in degrees, folded to
+    min(e, 180 - e) (the sign ambiguity of an essential-matrix estimate), the norm of their difference, and the rotation angle of
+    R_pred^T R_gt in degrees.  Any leading batch dimensions; the results have their shape."""
+    R_gt, t_gt = pose_gt[..., :3, :3], pose_gt[..., :3, 3]
+    R, t = pose_pred[..., :3, :3], pose_pred[..., :3, 3]
+    cos_t = ((t * t_gt).sum(-1) / (t.norm(dim=-1) * t_gt.norm(dim=-1))).clamp(-1.0, 1.0)
+    error_t = torch.rad2deg(torch.acos(cos_t))
+    error_t = torch.minimum(error_t, 180 - error_t)
+    error_t_scale = (t - t_gt).norm(dim=-1)
+    cos_r = (((R * R_gt).sum(dim=(-2, -1)) - 1) / 2).clamp(-1.0, 1.0)          # trace(R^T R_gt) = sum_ij R_ij R_gt_ij
+    error_R = torch.rad2deg(torch.abs(torch.acos(cos_r)))
+    return error_t, error_t_scale, error_R
+
+
+def pose_auc(errors, thresholds):
+    """area under the recall-over-error curve up to each threshold, divided by the threshold (the pose-AUC of the NoPoSplat tables)"""
+    import numpy as np
+    e = np.sort(np.asarray(errors, dtype=np.float64).reshape(-1))
+    recall = (np.arange(len(e)) + 1) / len(e)
+    e, recall = np.r_[0.0, e], np.r_[0.0, recall]
+    aucs = []
+    for t in thresholds:
+        last = np.searchsorted(e, t)
+        r, x = np.r_[recall[:last], recall[last - 1]], np.r_[e[:last], t]
+        aucs.append(float(np.sum(0.5 * (r[1:] + r[:-1]) * np.diff(x)) / t))
+    return aucs
