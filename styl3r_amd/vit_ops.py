@@ -28,12 +28,13 @@ import ctypes as C
 import os
 import subprocess
 import threading
-import weakref
 from pathlib import Path
 from typing import Optional
 
 import torch
 from torch import Tensor, nn
+
+from .weak_cache import WeakTensorCache
 
 _PKG = Path(__file__).resolve().parent
 _CSRC = _PKG / "csrc"
@@ -54,14 +55,14 @@ def _headers() -> list[Path]:
 
 def build_deps() -> list[Path]:
     """the files the library stamp covers: the sources and every header they compile against (editing one rebuilds the library)"""
-    return [_CSRC / s for s in _SOURCES if (_CSRC / s).exists()] + _headers()
+    return [_CSRC / s for s in _SOURCES] + _headers()
 
 
 def build_library(force: bool = False, verbose: bool = False) -> Path:
     """hipcc --offload-arch=gfx950 of csrc/vit_*.hip into lib/libvit_hip.so; rebuilt whenever the digest of
     (sources, headers, command line) differs from the stamp written next to the library (same scheme as _lib.py)."""
     from ._lib import sources_digest
-    names = [s for s in _SOURCES if (_CSRC / s).exists()]
+    names = list(_SOURCES)               # (a missing kernel file fails the build: nothing is left out quietly)
     deps = build_deps()
     extra = os.environ.get("VIT_HIPCC_EXTRA", "").split()          # kernel-experiment builds (tools/ only, with VIT_LIB_NAME)
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", *extra, *names, "-o", LIB_PATH.name]
@@ -139,9 +140,8 @@ def load() -> C.CDLL:
     lib.vit_rope2d.restype = C.c_int
     lib.vit_attention_fwd.argtypes = [C.POINTER(VitAttnArgs), vp, vp, vp, vp, vp, vp]
     lib.vit_attention_fwd.restype = C.c_int
-    if hasattr(lib, "vit_attention_bwd"):
-        lib.vit_attention_bwd.argtypes = [C.POINTER(VitAttnArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        lib.vit_attention_bwd.restype = C.c_int
+    lib.vit_attention_bwd.argtypes = [C.POINTER(VitAttnArgs), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vit_attention_bwd.restype = C.c_int
     lib.vit_linear_fwd.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.vit_linear_fwd.restype = C.c_int
     lib.vit_split_weight_bytes.argtypes = [C.c_int, C.c_int]
@@ -251,11 +251,15 @@ def _check(rc: int, what: str):
         raise RuntimeError(f"{what} failed: {ERRORS.get(rc, rc)} {load().vit_last_error().decode()}")
 
 
+def _device_stream(dev) -> tuple:
+    """(device index, raw handle of its current stream).  The raw-stream query is ~10x cheaper than torch.cuda.current_stream(dev).cuda_stream:
+    at batch-1 inference the host issues ~900 launches per forward and is the limit (tools/probes/infer_host_time.py)"""
+    idx = dev.index if dev.index is not None else torch.cuda.current_device()
+    return idx, torch._C._cuda_getCurrentRawStream(idx)
+
+
 def _stream(dev):
-    # (the raw-stream query is ~10x cheaper than torch.cuda.current_stream(dev).cuda_stream: at batch-1 inference the
-    # host issues ~900 of these launches per forward and is the limit, tools/probes/infer_host_time.py)
-    idx = dev.index
-    return C.c_void_p(torch._C._cuda_getCurrentRawStream(idx if idx is not None else torch.cuda.current_device()))
+    return C.c_void_p(_device_stream(dev)[1])
 
 
 def _need_gpu(t: Tensor, what: str):
@@ -431,8 +435,6 @@ class _Attention(torch.autograd.Function):
         q, k, v, out, lse, qpos, kpos = ctx.saved_tensors
         scale, base, max_pos = ctx.cfg
         lib = load()
-        if not hasattr(lib, "vit_attention_bwd"):
-            raise RuntimeError("vit_attention_bwd is not built into libvit_hip.so")
         _sync_attention_arith(ctx.arith)
         g = g.contiguous()
         dq = torch.empty(q.shape, dtype=torch.float32, device=q.device)
@@ -556,11 +558,7 @@ def _x6() -> bool:
         return False
     if LINEAR_MODE not in _PRODUCTS:
         raise ValueError(f"VIT_LINEAR_MODE = {LINEAR_MODE!r}: expected bf16x6, bf16x3, f16x3 or f32")
-    want = _PRODUCTS[LINEAR_MODE]
-    lib = load()
-    if lib.vit_x6_products() != want:
-        _check(lib.vit_x6_set_products(want), "vit_x6_set_products")
-    _sync_small_m()
+    _pin_products(LINEAR_MODE)
     return True
 
 def _pin_products(mode: str) -> None:
@@ -575,7 +573,7 @@ def _pin_products(mode: str) -> None:
         _sync_small_m()
 
 
-_SPLIT_CACHE: dict = {}   # (id(weight), layout[, "f16"]) -> (weakref(weight), weight._version, data_ptr, packed uint8 tensor)
+_SPLIT_CACHE = WeakTensorCache()   # _image_key(weight, layout) -> packed uint8 image of that weight (owner: the weight)
 
 
 def _f16() -> bool:
@@ -599,9 +597,7 @@ class _AmaxArena:
         the main stream already folded maxima into it).  Under hipGraph capture the arena is a fresh buffer of the graph's pool whose fill
         KERNEL (not a memset node: DESIGN R3.6) is captured in front of the producers, so every replay starts from zeroed words; the graph's
         pool keeps the memory for the graph's lifetime.  The stream key is the raw handle (~0.1 us), not torch.cuda.current_stream."""
-        idx = dev.index if dev.index is not None else torch.cuda.current_device()
-        capturing = torch.cuda.is_current_stream_capturing()
-        key = (idx, torch._C._cuda_getCurrentRawStream(idx), capturing)
+        key = (*_device_stream(dev), torch.cuda.is_current_stream_capturing())
         i = self.next.get(key, self.lines)
         if i >= self.lines:
             self.buf[key] = torch.empty(self.lines * self.LINE, dtype=torch.int32, device=dev).fill_(0)
@@ -629,21 +625,13 @@ def _amax_word(t: Tensor) -> Tensor:
 # |max| words PUBLISHED by the kernel that produced a tensor (vit_x6_set_output_amax: LayerNorm forward / backward, the GEMM and halo-convolution
 # epilogues): the f16x3 consumer of that tensor finds the word here instead of running a vit_amax pass.  Keyed by the tensor's memory; an entry
 # holds a WEAK reference to the producing tensor object and is valid only while that object is alive (its memory cannot have been reused), still
-# starts at the same address and carries the version it was published with (no in-place write since).  Views / reshapes of the tensor match too.
-_PUBLISHED: dict = {}        # (data_ptr, numel) -> (weakref(tensor), _version, word, raw stream it was published on)
+# starts at the same address and carries the version it was published with (no in-place write since).  Views / reshapes of the tensor match too:
+# the entries and their weak-reference callback are weak_cache's, the lookup rule is `_known_amax`'s own.
+_PUBLISHED = WeakTensorCache()        # (data_ptr, numel) -> word (owner: the produced tensor; stream: the raw stream it was published on)
 
 
 def _publish(t: Tensor, word: Tensor) -> None:
-    key = (t.data_ptr(), t.numel())
-
-    def drop(ref, key=key):
-        h = _PUBLISHED.get(key)
-        if h is not None and h[0] is ref:
-            del _PUBLISHED[key]
-    stream = 0
-    if t.is_cuda:
-        stream = torch._C._cuda_getCurrentRawStream(t.device.index if t.device.index is not None else torch.cuda.current_device())
-    _PUBLISHED[key] = (weakref.ref(t, drop), t._version, word, stream)
+    _PUBLISHED.store((t.data_ptr(), t.numel()), t, word, _device_stream(t.device)[1] if t.is_cuda else 0)
 
 
 PUBLISH_AMAX = os.environ.get("VIT_PUBLISH_AMAX", "1") == "1"      # A/B switch: 0 = every f16x3 operand scale comes from its own vit_amax pass
@@ -652,17 +640,15 @@ PUBLISH_AMAX = os.environ.get("VIT_PUBLISH_AMAX", "1") == "1"      # A/B switch:
 def _known_amax(t: Tensor) -> Optional[Tensor]:
     if not PUBLISH_AMAX:
         return None
-    hit = _PUBLISHED.get((t.data_ptr(), t.numel()))
+    hit = _PUBLISHED.entry((t.data_ptr(), t.numel()))
     if hit is None:
         return None
-    src = hit[0]()
-    if src is None or src.data_ptr() != t.data_ptr() or src._version != hit[1] or t._version != hit[1]:
+    src = hit()
+    if src is None or src.data_ptr() != t.data_ptr() or src._version != hit.version or t._version != hit.version:
         return None
-    if t.is_cuda:
-        idx = t.device.index if t.device.index is not None else torch.cuda.current_device()
-        if hit[3] != torch._C._cuda_getCurrentRawStream(idx) and not torch.cuda.is_current_stream_capturing():
-            hit[2].record_stream(torch.cuda.current_stream(t.device))     # word of another stream's arena read here: the allocator must know
-    return hit[2]
+    if t.is_cuda and hit.stream != _device_stream(t.device)[1] and not torch.cuda.is_current_stream_capturing():
+        hit.payload.record_stream(torch.cuda.current_stream(t.device))     # word of another stream's arena read here: the allocator must know
+    return hit.payload
 
 
 def _amax_of(t: Tensor) -> Tensor:
@@ -675,44 +661,34 @@ def _amax_of(t: Tensor) -> Tensor:
     return _amax_word(t)
 
 
-def _want_output_amax(dev) -> Optional[Tensor]:
-    """f16x3: ask the NEXT launch on this thread (Linear / halo convolution / LayerNorm) to publish the |max| of what it stores"""
-    if not (_f16() and PUBLISH_AMAX):
-        return None
+def _output_amax_word(dev) -> Tensor:
+    """a zeroed |max| word that the NEXT launch on this thread (Linear / halo convolution / LayerNorm) folds the |max| of what it stores into"""
     w = _AMAX.word(dev)
     _check(load().vit_x6_set_output_amax(w.data_ptr()), "vit_x6_set_output_amax")
     return w
 
 
-_WEIGHT_AMAX: dict = {}      # id(weight) -> (weakref, _version, data_ptr, |max| word): one vit_amax pass per weight and optimizer step
+def _want_output_amax(dev) -> Optional[Tensor]:
+    """f16x3: ask the next launch to publish its output's |max|, unless the A/B switch is off"""
+    return _output_amax_word(dev) if (_f16() and PUBLISH_AMAX) else None
+
+
+_WEIGHT_AMAX = WeakTensorCache()      # id(weight) -> |max| word of the weight's values: one vit_amax pass per weight and optimizer step
 
 
 def _weight_amax_word(weight: Tensor, values: Tensor) -> Tensor:
     """|max| word of a parameter (`values`: the fp32 tensor whose elements are the parameter's -- any permutation of them), cached like
     its split images: the forward, transposed and convolution images of one weight share it"""
-    key = id(weight)
-    hit = _WEIGHT_AMAX.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
-
-    def drop(ref, key=key):
-        h = _WEIGHT_AMAX.get(key)
-        if h is not None and h[0] is ref:
-            del _WEIGHT_AMAX[key]
-    word = _amax_word(values)
-    _WEIGHT_AMAX[key] = (weakref.ref(weight, drop), weight._version, weight.data_ptr(), word)
+    word = _WEIGHT_AMAX.get(id(weight), weight)
+    if word is None:
+        word = _amax_word(values)
+        _WEIGHT_AMAX.store(id(weight), weight, word)
     return word
 
 
 def register_weight_amax(weight: Tensor, word: Tensor) -> None:
     """the |max| word of `weight`'s CURRENT values, produced elsewhere (optim.AdamWHIP: csrc/vit_optim.hip folds it while it writes the update)"""
-    key = id(weight)
-
-    def drop(ref, key=key):
-        h = _WEIGHT_AMAX.get(key)
-        if h is not None and h[0] is ref:
-            del _WEIGHT_AMAX[key]
-    _WEIGHT_AMAX[key] = (weakref.ref(weight, drop), weight._version, weight.data_ptr(), word)
+    _WEIGHT_AMAX.store(id(weight), weight, word)
 
 
 def _announce(a: Optional[Tensor], b: Optional[Tensor] = None) -> None:
@@ -721,14 +697,16 @@ def _announce(a: Optional[Tensor], b: Optional[Tensor] = None) -> None:
            "vit_x6_set_operand_amax")
 
 
-def _dead_entry_ref(weight: Tensor, key):
-    """weak reference whose callback drops the cache entry (and its packed buffer) the moment the tensor dies: per-step temporaries
-    (the reshaped ConvTranspose / strided-conv weights of the DPT reassemble stage) must not pile up in the cache"""
-    def drop(ref, key=key):
-        hit = _SPLIT_CACHE.get(key)
-        if hit is not None and hit[0] is ref:
-            del _SPLIT_CACHE[key]
-    return weakref.ref(weight, drop)
+# layout names of a weight image: MFMA operand order / block layout of the ring kernels (_t: the transposed image the dX GEMM reads), and
+# "conv" / "conv_dx" (the rearranged convolution weight / its flipped, channel-transposed form)
+_LINEAR_LAYOUTS = ("row", "row_t", "block", "block_t")      # [2 * block + transposed]
+
+
+def _image_key(weight: Tensor, layout: str) -> tuple:
+    """THE key of a weight image in _SPLIT_CACHE: the lazy splits, the pair splits, the one-launch refresh and the staleness probe of _FusedLinear.forward
+    all come here, so they cannot disagree (a refresh that spelled another key would find nothing and leave every image to one launch each: correct
+    results, ~1 270 launches a step).  The f16x3 image differs (two fp16 pieces of the scaled weight): the mode at call time is part of the key."""
+    return (id(weight), layout, "f16") if LINEAR_MODE == "f16x3" else (id(weight), layout)
 
 
 _SPLIT_JOB_DTYPE = None
@@ -756,15 +734,15 @@ def refresh_split_cache(params) -> int:
     if plan is not None:                                  # fast path
         ok = len(plan["params"]) == len(params) and all(a is b for a, b in zip(plan["params"], params))
         if ok:
-            cache, wam = _SPLIT_CACHE, _WEIGHT_AMAX
+            image, weight_word = _SPLIT_CACHE.entry, _WEIGHT_AMAX.entry
             for key, p, packed, word in plan["entries"]:
-                hit = cache.get(key)
-                if hit is None or hit[3] is not packed or hit[2] != p.data_ptr() or hit[1] == p._version:
-                    ok = False; why = ("image", key, hit is None, hit is not None and hit[3] is not packed, hit is not None and hit[1] == p._version); break
+                hit = image(key)
+                if hit is None or hit.payload is not packed or hit.ptr != p.data_ptr() or hit.version == p._version:
+                    ok = False; why = ("image", key, hit is None, hit is not None and hit.payload is not packed, hit is not None and hit.version == p._version); break
                 if word:                                  # (the optimizer hands in a fresh view of the same word every step: compare addresses)
-                    hw = wam.get(key[0])
-                    if hw is None or hw[3].data_ptr() != word or hw[1] != p._version:
-                        ok = False; why = ("word", key, hw is None, hw is not None and hw[1] != p._version); break
+                    hw = weight_word(id(p))
+                    if hw is None or hw.payload.data_ptr() != word or hw.version != p._version:
+                        ok = False; why = ("word", key, hw is None, hw is not None and hw.version != p._version); break
             if not ok and os.environ.get("VIT_SPLIT_DEBUG"):
                 print("refresh_split_cache: plan dropped:", why, flush=True)
         elif os.environ.get("VIT_SPLIT_DEBUG"):
@@ -772,8 +750,7 @@ def refresh_split_cache(params) -> int:
         if ok:
             _check(load().vit_split_weights_many(plan["table"].data_ptr(), plan["njobs"], plan["blocks"], _stream(dev)), "vit_split_weights_many")
             for key, p, packed, word in plan["entries"]:
-                hit = _SPLIT_CACHE[key]
-                _SPLIT_CACHE[key] = (hit[0], p._version, hit[2], packed)
+                _SPLIT_CACHE.renew(key, p)
             CALLS["split_many_images"] += plan["njobs"]
             CALLS["split_plan_reused"] += 1
             return plan["njobs"]
@@ -781,28 +758,27 @@ def refresh_split_cache(params) -> int:
     jobs, entries = [], []
     partial = False         # some image of some weight is not part of this refresh: the job table must not become the reusable plan
     for p in params:
-        pid, ver, ptr = id(p), p._version, p.data_ptr()
+        ver, ptr = p._version, p.data_ptr()
         word = None
         if f16:
-            hw = _WEIGHT_AMAX.get(pid)
-            if hw is None or hw[0]() is not p or hw[1] != ver or hw[2] != ptr:
+            word = _WEIGHT_AMAX.get(id(p), p)
+            if word is None:
                 partial = True
                 continue
-            word = hw[3]
         N, K = p.shape
         for transposed in (False, True):
             for block in (False, True):
-                key = ((pid, "block_t" if transposed else "block") if block else (pid, transposed)) + (("f16",) if f16 else ())
-                hit = _SPLIT_CACHE.get(key)
+                key = _image_key(p, _LINEAR_LAYOUTS[2 * block + transposed])
+                hit = _SPLIT_CACHE.entry(key)
                 if hit is None:
                     continue            # (a layout this weight never uses)
-                if hit[0]() is not p or hit[2] != ptr or hit[1] == ver:
+                if hit() is not p or hit.ptr != ptr or hit.version == ver:
                     partial = True      # an image that exists but is not refreshed here (already current, or of a replaced tensor)
                     continue
                 R, Kc = (K, N) if transposed else (N, K)
                 if Kc % 8:
                     continue
-                packed = hit[3]
+                packed = hit.payload
                 tail = packed.data_ptr() + ((R + 63) // 64 * 64 if block else R) * Kc * 6
                 jobs.append((ptr, packed.data_ptr(), word.data_ptr() if word is not None else 0, tail, N, K,
                              (1 if transposed else 0) | (2 if block else 0), (Kc + 63) // 64, (R + 63) // 64))
@@ -820,8 +796,7 @@ def refresh_split_cache(params) -> int:
     table = torch.from_numpy(host.view(np.uint8).reshape(-1).copy()).to(dev)
     _check(load().vit_split_weights_many(table.data_ptr(), len(jobs), first, _stream(dev)), "vit_split_weights_many")
     for key, p, packed, word in entries:
-        hit = _SPLIT_CACHE[key]
-        _SPLIT_CACHE[key] = (hit[0], p._version, p.data_ptr(), packed)
+        _SPLIT_CACHE.renew(key, p)
     # the plan is reusable only if it covers every cached image of every weight handed in (a table built on an early step, while the
     # cache was still filling or with some images already current, passed every fast-path check afterwards and pinned the rest to lazy launches)
     if not partial:
@@ -833,14 +808,43 @@ def refresh_split_cache(params) -> int:
 PAIR_SPLIT = os.environ.get("VIT_PAIR_SPLIT", "1") == "1"      # A/B switch: 0 = one launch per weight image (rounds 2-5)
 
 
-def _image_key(weight: Tensor, block: bool, transposed: bool) -> tuple:
-    if block:
-        return (id(weight), "block_t" if transposed else "block") + (("f16",) if _f16() else ())
-    return (id(weight), transposed, "f16") if _f16() else (id(weight), transposed)
+def _image_buffer(key: tuple, weight: Tensor, block: bool, transposed: bool) -> Tensor:
+    """where an image of a Linear `weight` is (re)built: the buffer of its previous image when that was this tensor's and has the size, else a new one"""
+    N, K = weight.shape
+    nbytes = load().vit_split_weight_block_bytes(N, K, 1 if transposed else 0) if block else load().vit_split_weight_bytes(N, K)
+    old = _SPLIT_CACHE.previous(key, weight)
+    return old if old is not None and old.numel() == nbytes else torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
 
 
-def _fresh(hit, weight: Tensor) -> bool:
-    return hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr()
+def _split_into(key: tuple, weight: Tensor, values: Tensor, packed: Tensor, kernel: str, transposed: bool = False) -> Tensor:
+    """the lazy path of every single-image split: `values` (rows, cols) -- the fp32 elements of `weight` as the kernel reads them -- split into
+    `packed` by vit_split_weight / vit_split_weight_block and stored under `key`; f16x3: the weight's |max| word is announced first"""
+    if _f16():
+        _announce(_weight_amax_word(weight, values))
+    _check(getattr(load(), kernel)(values.data_ptr(), packed.data_ptr(), *values.shape, 1 if transposed else 0, _stream(weight.device)), kernel)
+    _SPLIT_CACHE.store(key, weight, packed)
+    return packed
+
+
+def _linear_image(weight: Tensor, block: bool, transposed: bool) -> Tensor:
+    key = _image_key(weight, _LINEAR_LAYOUTS[2 * block + transposed])
+    hit = _SPLIT_CACHE.get(key, weight)
+    if hit is not None:
+        return hit
+    return _split_into(key, weight, weight.detach().contiguous().float(), _image_buffer(key, weight, block, transposed),
+                       "vit_split_weight_block" if block else "vit_split_weight", transposed)
+
+
+def split_weight(weight: Tensor, transposed: bool = False) -> Tensor:
+    """bf16x3 split of an nn.Linear weight (N,K) in MFMA operand order (include/vit_ops.h vit_split_weight); cached until the parameter is
+    modified in place or replaced (weak_cache: weak reference + version counter + address; optimizer steps must bump the version)."""
+    return _linear_image(weight, False, transposed)
+
+
+def split_weight_block(weight: Tensor, transposed: bool = False) -> Tensor:
+    """bf16x3 split of a weight (N,K) in the BLOCK layout of csrc/vit_gemm_x6r.hip (vit_split_weight_block; rows padded to a
+    multiple of 64 with zeros).  Cached like `split_weight`."""
+    return _linear_image(weight, True, transposed)
 
 
 def split_weight_pair(weight: Tensor, block_fwd: bool, block_t: bool) -> None:
@@ -848,45 +852,17 @@ def split_weight_pair(weight: Tensor, block_fwd: bool, block_t: bool) -> None:
     (vit_split_weight_pair), each in the layout its kernel wants (block: the LDS-DMA ring kernels; row: vit_linear_x6_fwd).  Called by the
     forward of a layer whose input needs a gradient when the forward image is stale (i.e. once per optimizer step and weight): the
     backward then finds its image in the cache.  Entries are the same as the single-image functions write."""
-    lib = load()
     N, K = weight.shape
     w = weight.detach().contiguous().float()
-    keys = (_image_key(weight, block_fwd, False), _image_key(weight, block_t, True))
-    sizes = (lib.vit_split_weight_block_bytes(N, K, 0) if block_fwd else lib.vit_split_weight_bytes(N, K),
-             lib.vit_split_weight_block_bytes(N, K, 1) if block_t else lib.vit_split_weight_bytes(N, K))
-    bufs = []
-    for key, nbytes in zip(keys, sizes):
-        hit = _SPLIT_CACHE.get(key)
-        reuse = hit is not None and hit[0]() is weight and hit[3].numel() == nbytes
-        bufs.append(hit[3] if reuse else torch.empty(nbytes, dtype=torch.uint8, device=weight.device))
+    keys = (_image_key(weight, _LINEAR_LAYOUTS[2 * block_fwd]), _image_key(weight, _LINEAR_LAYOUTS[2 * block_t + 1]))
+    bufs = (_image_buffer(keys[0], weight, block_fwd, False), _image_buffer(keys[1], weight, block_t, True))
     if _f16():
         _announce(_weight_amax_word(weight, w))
-    _check(lib.vit_split_weight_pair(w.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(), N, K, 1 if block_fwd else 0, 1 if block_t else 0,
-                                     _stream(weight.device)), "vit_split_weight_pair")
+    _check(load().vit_split_weight_pair(w.data_ptr(), bufs[0].data_ptr(), bufs[1].data_ptr(), N, K, 1 if block_fwd else 0, 1 if block_t else 0,
+                                        _stream(weight.device)), "vit_split_weight_pair")
     CALLS["split_pair"] += 1
     for key, buf in zip(keys, bufs):
-        _SPLIT_CACHE[key] = (_dead_entry_ref(weight, key), weight._version, weight.data_ptr(), buf)
-
-
-def split_weight_block(weight: Tensor, transposed: bool = False) -> Tensor:
-    """bf16x3 split of a weight (N,K) in the BLOCK layout of csrc/vit_gemm_x6r.hip (vit_split_weight_block; rows padded to a
-    multiple of 64 with zeros).  Cached like `split_weight` (weak reference + version counter)."""
-    key = (id(weight), "block_t" if transposed else "block") + (("f16",) if _f16() else ())
-    hit = _SPLIT_CACHE.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
-    lib = load()
-    N, K = weight.shape
-    w = weight.detach().contiguous().float()
-    nbytes = lib.vit_split_weight_block_bytes(N, K, 1 if transposed else 0)
-    reuse = hit is not None and hit[0]() is weight and hit[3].numel() == nbytes
-    packed = hit[3] if reuse else torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    if _f16():
-        _announce(_weight_amax_word(weight, w))
-    _check(lib.vit_split_weight_block(w.data_ptr(), packed.data_ptr(), N, K, 1 if transposed else 0, _stream(weight.device)),
-           "vit_split_weight_block")
-    _SPLIT_CACHE[key] = (_dead_entry_ref(weight, key), weight._version, weight.data_ptr(), packed)
-    return packed
+        _SPLIT_CACHE.store(key, weight, buf)
 
 
 def linear_x6r(x: Tensor, packed_block: Tensor, N: int, bias: Optional[Tensor] = None, residual: Optional[Tensor] = None,
@@ -904,74 +880,40 @@ def linear_x6r(x: Tensor, packed_block: Tensor, N: int, bias: Optional[Tensor] =
     return out.reshape(*x.shape[:-1], N)
 
 
-def split_weight(weight: Tensor, transposed: bool = False) -> Tensor:
-    """bf16x3 split of an nn.Linear weight (N,K) in MFMA operand order (include/vit_ops.h vit_split_weight); cached until
-    the parameter is modified in place or replaced: `load_state_dict` and in-place torch ops bump `Tensor._version`; optimizer steps do
-    NOT by themselves (optim.AdamWHIP writes through raw pointers, and the framework's fused AdamW leaves the counter alone, too), so
-    AdamWHIP.step and train.make_optimizer's post-step hook bump it explicitly (without that the kernels kept computing with the
-    first split of every weight).  The entry
-    holds a weak reference: a new tensor that happens to reuse a dead one's id / address never hits it.  Writes through
-    `weight.data` bypass the version counter -- call `invalidate_split_cache()` after such surgery."""
-    key = (id(weight), transposed, "f16") if _f16() else (id(weight), transposed)    # (the f16x3 image differs: two fp16 pieces of the scaled weight)
-    hit = _SPLIT_CACHE.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
-    lib = load()
-    N, K = weight.shape
-    w = weight.detach().contiguous().float()
-    nbytes = lib.vit_split_weight_bytes(N, K)
-    reuse = hit is not None and hit[0]() is weight and hit[3].numel() == nbytes
-    packed = hit[3] if reuse else torch.empty(nbytes, dtype=torch.uint8, device=weight.device)
-    if _f16():
-        _announce(_weight_amax_word(weight, w))
-    _check(lib.vit_split_weight(w.data_ptr(), packed.data_ptr(), N, K, 1 if transposed else 0, _stream(weight.device)),
-           "vit_split_weight")
-    _SPLIT_CACHE[key] = (_dead_entry_ref(weight, key), weight._version, weight.data_ptr(), packed)
-    return packed
-
-
 def split_conv_weight(weight: Tensor, for_input_grad: bool = False, want_dx: bool = False) -> Tensor:
     """bf16x3 split of a conv weight (Co,Ci,k,k) rearranged for vit_conv_x6_fwd: (Co, k*k*Ci) with k index = tap*Ci + ci;
     `for_input_grad`: the spatially flipped, channel-transposed weight (Ci, k*k*Co) whose convolution with dY is dX.
     Cached like `split_weight` (weak reference + version counter of the ORIGINAL parameter).
     Round 6: 1x1 / 3x3 weights are rearranged and split by ONE kernel straight from the parameter (vit_split_conv_weight_pair) -- and when
     the forward finds its image stale and says its input needs a gradient (`want_dx`), the dX image comes out of the same launch."""
-    key = (id(weight), "conv_dx" if for_input_grad else "conv") + (("f16",) if _f16() else ())
-    hit = _SPLIT_CACHE.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == weight._version and hit[2] == weight.data_ptr():
-        return hit[3]
+    key = _image_key(weight, "conv_dx" if for_input_grad else "conv")
+    hit = _SPLIT_CACHE.get(key, weight)
+    if hit is not None:
+        return hit
     lib = load()
     Co, Ci, kh, kw = weight.shape
-    if PAIR_SPLIT and kh == kw and kh in (1, 3) and Ci % 8 == 0 and weight.dtype == torch.float32 and weight.is_contiguous():
-        both = (want_dx or for_input_grad) and Co % 8 == 0
-        if for_input_grad and not both:
-            pass            # (a dX image of a weight whose Co is not a multiple of 8: the rearranged-copy path below)
-        else:
-            w = weight.detach()
-            kf, kd = (id(weight), "conv") + (("f16",) if _f16() else ()), (id(weight), "conv_dx") + (("f16",) if _f16() else ())
-            pf = torch.empty(lib.vit_split_weight_bytes(Co, kh * kw * Ci), dtype=torch.uint8, device=weight.device)
-            pd = torch.empty(lib.vit_split_weight_bytes(Ci, kh * kw * Co), dtype=torch.uint8, device=weight.device) if both else None
-            if _f16():
-                _announce(_weight_amax_word(weight, w))
-            _check(lib.vit_split_conv_weight_pair(w.data_ptr(), pf.data_ptr(), pd.data_ptr() if pd is not None else None, Co, Ci, kh,
-                                                  _stream(weight.device)), "vit_split_conv_weight_pair")
-            CALLS["split_pair"] += 1
-            _SPLIT_CACHE[kf] = (_dead_entry_ref(weight, kf), weight._version, weight.data_ptr(), pf)
-            if pd is not None:
-                _SPLIT_CACHE[kd] = (_dead_entry_ref(weight, kd), weight._version, weight.data_ptr(), pd)
-            return pd if for_input_grad else pf
+    both = (want_dx or for_input_grad) and Co % 8 == 0
+    # (a dX image of a weight whose Co is not a multiple of 8: the rearranged-copy path below)
+    if PAIR_SPLIT and kh == kw and kh in (1, 3) and Ci % 8 == 0 and weight.dtype == torch.float32 and weight.is_contiguous() and (both or not for_input_grad):
+        w = weight.detach()
+        pf = torch.empty(lib.vit_split_weight_bytes(Co, kh * kw * Ci), dtype=torch.uint8, device=weight.device)
+        pd = torch.empty(lib.vit_split_weight_bytes(Ci, kh * kw * Co), dtype=torch.uint8, device=weight.device) if both else None
+        if _f16():
+            _announce(_weight_amax_word(weight, w))
+        _check(lib.vit_split_conv_weight_pair(w.data_ptr(), pf.data_ptr(), pd.data_ptr() if pd is not None else None, Co, Ci, kh,
+                                              _stream(weight.device)), "vit_split_conv_weight_pair")
+        CALLS["split_pair"] += 1
+        _SPLIT_CACHE.store(_image_key(weight, "conv"), weight, pf)
+        if pd is not None:
+            _SPLIT_CACHE.store(_image_key(weight, "conv_dx"), weight, pd)
+        return pd if for_input_grad else pf
     w = weight.detach().float()
     if for_input_grad:
         w2 = w.flip(2, 3).permute(1, 2, 3, 0).reshape(Ci, kh * kw * Co).contiguous()
     else:
         w2 = w.permute(0, 2, 3, 1).reshape(Co, kh * kw * Ci).contiguous()
-    R, Kc = w2.shape
-    packed = torch.empty(lib.vit_split_weight_bytes(R, Kc), dtype=torch.uint8, device=weight.device)
-    if _f16():
-        _announce(_weight_amax_word(weight, w2))
-    _check(lib.vit_split_weight(w2.data_ptr(), packed.data_ptr(), R, Kc, 0, _stream(weight.device)), "vit_split_weight")
-    _SPLIT_CACHE[key] = (_dead_entry_ref(weight, key), weight._version, weight.data_ptr(), packed)
-    return packed
+    packed = torch.empty(lib.vit_split_weight_bytes(*w2.shape), dtype=torch.uint8, device=weight.device)
+    return _split_into(key, weight, w2, packed, "vit_split_weight")
 
 
 def conv_x6_forward(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, residual: Optional[Tensor] = None,
@@ -1422,7 +1364,7 @@ class _UpsampleAddRelu(torch.autograd.Function):
         return dx, dc
 
 
-_DERIVED: dict = {}      # (id(parameter), tag) -> (weakref(parameter), version, data_ptr, derived tensor)
+_DERIVED = WeakTensorCache()      # (id(parameter), tag) -> derived tensor (owner: the parameter)
 
 
 def derived_weight(param: Optional[Tensor], tag: str, fn):
@@ -1435,17 +1377,11 @@ def derived_weight(param: Optional[Tensor], tag: str, fn):
     if torch.is_grad_enabled() and param.requires_grad:
         return fn(param)
     key = (id(param), tag)
-    hit = _DERIVED.get(key)
-    if hit is not None and hit[0]() is param and hit[1] == param._version and hit[2] == param.data_ptr():
-        return hit[3]
-
-    def drop(ref, key=key):
-        h = _DERIVED.get(key)
-        if h is not None and h[0] is ref:
-            del _DERIVED[key]
-    with torch.no_grad():
-        d = fn(param.detach())
-    _DERIVED[key] = (weakref.ref(param, drop), param._version, param.data_ptr(), d)
+    d = _DERIVED.get(key, param)
+    if d is None:
+        with torch.no_grad():
+            d = fn(param.detach())
+        _DERIVED.store(key, param, d)
     return d
 
 
@@ -1573,6 +1509,13 @@ def _ring_cfg(M: int, N: int, K: int) -> int:
     return (_RING_SHAPES if M >= 4096 else _RING_SHAPES_MID).get(LINEAR_MODE, {}).get((N, K), 0)
 
 
+def _ring_cfg_dx(M: int, N: int, K: int) -> int:
+    """... of the input-gradient GEMM of a Linear (N, K), for the forward (which image a pair split builds) and the backward (which kernel reads it):
+    ring kernels in three-product mode only (in six-product mode the A/B on the whole step lost 3 ms), the narrow-output kernel (5) in every mode"""
+    ring = _ring_cfg(M, K, N)
+    return ring if (ring == 5 or LINEAR_MODE in ("bf16x3", "f16x3")) else 0
+
+
 class _FusedLinear(torch.autograd.Function):
     """forward on the hand-written MFMA kernels (f32 or bf16x6); backward in bf16x6 mode: dX with the pre-split transposed
     weight, dW = dY^T X and db in one split-M pass (vit_linear_x6_wgrad); in f32 mode the backward GEMMs are plain library
@@ -1611,18 +1554,14 @@ class _FusedLinear(torch.autograd.Function):
             ctx.ax = link_in.ax if (link_in is not None and link_in.ax is not None) else _amax_of(x2)
             _announce(ctx.ax)
             if publish:
-                link.ax = _AMAX.word(x2.device)
-                _check(load().vit_x6_set_output_amax(link.ax.data_ptr()), "vit_x6_set_output_amax")
+                link.ax = _output_amax_word(x2.device)
             elif amax_out and PUBLISH_AMAX and ring in (0, 1, 3, 5) and act == 0:
-                out_word = _AMAX.word(x2.device)
-                _check(load().vit_x6_set_output_amax(out_word.data_ptr()), "vit_x6_set_output_amax")
-        if x6 and PAIR_SPLIT and x.requires_grad and N % 16 == 0 and K % 8 == 0 and not _fresh(_SPLIT_CACHE.get(_image_key(weight, bool(ring), False)), weight):
+                out_word = _output_amax_word(x2.device)
+        if (x6 and PAIR_SPLIT and x.requires_grad and N % 16 == 0 and K % 8 == 0
+                and _SPLIT_CACHE.get(_image_key(weight, "block" if ring else "row"), weight) is None):
             # the forward image is stale (the optimizer stepped): the backward's input-gradient GEMM will need the transposed image of the
             # same values -- both in one launch, each in the layout its kernel takes (the dX dispatch rule of `backward` below)
-            ring_dx = _ring_cfg(M, K, N)
-            if ring_dx != 5 and LINEAR_MODE not in ("bf16x3", "f16x3"):
-                ring_dx = 0
-            split_weight_pair(weight, bool(ring), bool(ring_dx))
+            split_weight_pair(weight, bool(ring), bool(_ring_cfg_dx(M, N, K)))
         if ring:
             # LDS-DMA ring kernels (csrc/vit_gemm_x6r.hip), bit-identical to vit_linear_x6_fwd: taken on the shapes where
             # tools/probes/gemm_lab.py measured them faster (per arithmetic mode: _RING_SHAPES)
@@ -1682,12 +1621,10 @@ class _FusedLinear(torch.autograd.Function):
             nonlocal dx_word
             # (fc2, GELU' in the epilogue: the stored values ARE fc1's dY)
             if f16 and lk is not None and gelu_pre is not None and ring in (0, 1, 3, 5):
-                lk.adx = _AMAX.word(g.device)
-                _check(load().vit_x6_set_output_amax(lk.adx.data_ptr()), "vit_x6_set_output_amax")
+                lk.adx = _output_amax_word(g.device)
             elif f16 and ctx.amax_dx and PUBLISH_AMAX and gelu_pre is None and ring in (0, 1, 3, 5):
                 # (proj: its input gradient is the attention backward's dO, whose f16x3 scale comes from this word)
-                dx_word = _AMAX.word(g.device)
-                _check(load().vit_x6_set_output_amax(dx_word.data_ptr()), "vit_x6_set_output_amax")
+                dx_word = _output_amax_word(g.device)
         dx = None
         if need_x:
             N, K = w.shape
@@ -1696,10 +1633,7 @@ class _FusedLinear(torch.autograd.Function):
                 dx = torch.empty((g2c.shape[0], K), dtype=torch.float32, device=g.device)
                 lk = ctx.link_in
                 gelu_pre = lk.pre if (lk is not None and lk.pre is not None and tuple(lk.pre.shape) == (g2c.shape[0], K)) else None
-                # (input-gradient GEMMs take the ring kernels in three-product mode only: in six-product mode the A/B on the whole step lost 3 ms)
-                ring = _ring_cfg(g2c.shape[0], K, N) if ctx.mode == LINEAR_MODE else 0
-                if ring != 5 and ctx.mode not in ("bf16x3", "f16x3"):
-                    ring = 0
+                ring = _ring_cfg_dx(g2c.shape[0], N, K) if ctx.mode == LINEAR_MODE else 0
                 if ring:
                     CALLS["linear_x6r"] += 1
                     wpb = split_weight_block(ctx.weight_ref, True)
@@ -1836,8 +1770,7 @@ def fused_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, resid
             # the small-M kernel (csrc/vit_gemm_sm.hip) runs the whole epilogue in one launch, GELU included: every output gets its |max| word
             # for free (the next Linear / the attention finds it published); the 128-row kernel publishes un-activated outputs on request
             if PUBLISH_AMAX and ((amax_out and not gelu) or small):
-                ow = _AMAX.word(x2.device)
-                _check(load().vit_x6_set_output_amax(ow.data_ptr()), "vit_x6_set_output_amax")
+                ow = _output_amax_word(x2.device)
         if small:
             CALLS["linear_sm"] = CALLS.get("linear_sm", 0) + 1
             _check(load().vit_linear_x6r_fwd(x2.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else None,
@@ -1889,8 +1822,7 @@ def grouped_linear(x: Tensor, layers, residual: Optional[Tensor] = None, gelu: b
     if _f16():
         _announce(_amax_of(x))
         if PUBLISH_AMAX:
-            ow = _AMAX.word(x.device)
-            _check(load().vit_x6_set_output_amax(ow.data_ptr()), "vit_x6_set_output_amax")
+            ow = _output_amax_word(x.device)
     xb, ob, eb = x.data_ptr(), out.data_ptr(), 4
     xs = [xb + (1 if flip else 0) * M * K * eb, xb + (0 if flip else 1) * M * K * eb]
     os_ = [ob, ob + M * N * eb]

@@ -311,3 +311,59 @@ def test_edge_pixel_rule_of_the_e2e_image_comparison():
         many[0, 0, 2, 5 + dy, 5 + dx] += 0.01
     with pytest.raises(AssertionError):
         _edge_pixels(many, ref, ok, bar=1e-3)
+
+
+def test_weak_tensor_cache_follows_object_version_and_address():
+    """weak_cache.WeakTensorCache, the one validity rule behind vit_ops._SPLIT_CACHE / _WEIGHT_AMAX / _DERIVED / _PUBLISHED, on plain CPU tensors:
+    a payload is served for the same tensor object at the same version and address only; the previous payload of the same live owner stays
+    reachable for buffer reuse; an entry goes with its owner -- but never takes a newer owner's entry under the same key with it"""
+    import gc
+    from styl3r_amd.weak_cache import WeakTensorCache
+    cache = WeakTensorCache()
+    w, other = torch.randn(4, 6), torch.randn(4, 6)
+    cache.store("k", w, "image")
+    assert len(cache) == 1 and "k" in cache and "other" not in cache
+    assert cache.get("k", w) == "image"                                         # same object, version and address
+    assert cache.get("k", other) is None and cache.previous("k", other) is None # another tensor asking under the same key
+    assert cache.get("missing", w) is None and cache.previous("missing", w) is None
+    e = cache.entry("k")
+    assert e() is w and e.key == "k" and e.version == w._version and e.ptr == w.data_ptr() and e.payload == "image" and e.stream == 0
+    w.add_(1.0)                                                                 # an in-place op: the version moves
+    assert cache.get("k", w) is None
+    assert cache.previous("k", w) == "image"                                    # ... the old payload (its buffer) is still the owner's
+    cache.renew("k", w)                                                         # rebuilt in place: current again at the present version
+    assert cache.get("k", w) == "image"
+    w.data = torch.randn(4, 6)                                                  # same object, same version, other memory
+    assert cache.get("k", w) is None and cache.previous("k", w) == "image"
+    cache.store("k", other, "other image")                                      # a newer owner takes the key ...
+    assert cache.get("k", other) == "other image" and cache.get("k", w) is None and cache.previous("k", w) is None
+    del w
+    gc.collect()
+    assert cache.get("k", other) == "other image"                               # ... and survives the older owner's death (the `is ref` guard)
+    del other
+    gc.collect()
+    assert "k" not in cache and len(cache) == 0                                 # the entry went with its owner
+    a, b = torch.randn(2), torch.randn(2)
+    cache.store(1, a, "a"); cache.store(2, b, "b", stream=7)
+    assert len(cache) == 2 and cache.entry(2).stream == 7
+    cache.clear()
+    assert len(cache) == 0 and 1 not in cache and cache.get(1, a) is None and cache.entry(2) is None
+    del a, b
+    gc.collect()                                                                # callbacks of cleared entries find nothing and do nothing
+    assert len(cache) == 0
+
+
+def test_weight_image_keys_are_distinct_per_layout_and_mode(monkeypatch):
+    """vit_ops._image_key is the only place that spells a _SPLIT_CACHE key: six layouts x {f16x3, any other mode} give twelve distinct keys for
+    one weight (the f16x3 images hold other bytes), the three non-f16 modes share theirs, and another weight shares none"""
+    from styl3r_amd import vit_ops
+    layouts = ("row", "row_t", "block", "block_t", "conv", "conv_dx")
+    assert vit_ops._LINEAR_LAYOUTS == layouts[:4]
+    w, w2 = torch.zeros(8, 8), torch.zeros(8, 8)
+    keys = {}
+    for mode in ("f16x3", "bf16x6", "bf16x3", "f32"):
+        monkeypatch.setattr(vit_ops, "LINEAR_MODE", mode)
+        keys[mode] = [vit_ops._image_key(w, l) for l in layouts]
+        assert not set(keys[mode]) & {vit_ops._image_key(w2, l) for l in layouts}
+    assert len(set(keys["f16x3"]) | set(keys["bf16x6"])) == 12
+    assert keys["bf16x6"] == keys["bf16x3"] == keys["f32"]
