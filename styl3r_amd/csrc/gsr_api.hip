@@ -4,18 +4,6 @@
 #include "gsr_common.h"
 
 namespace gsr {
-int layout(const GsrDims &d, long long cap, GsrLayout &L);
-int forward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *opac,
-            const float *shs, long long cap, void *workspace, size_t workspace_bytes, float *image, float *depth,
-            float *opacity, int32_t *radii, int32_t *n_touched, int32_t *status, const GsrFused *fx, hipStream_t stream,
-            bool composite = true);
-int backward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *shs,
-             long long cap, void *workspace, size_t workspace_bytes, const float *dL_dimage, const float *dL_ddepth,
-             float *dL_dmeans, float *dL_dcov6, float *dL_dopac, float *dL_dshs, float *dL_dmeans2D, float *dL_dtau,
-             const GsrFused *fx, hipStream_t stream);
-}  // namespace gsr
-
-namespace gsr {
 thread_local hipError_t g_last_hip_error = hipSuccess;
 
 // ---- view set-up kernel: one thread per view ---------------------------------------------

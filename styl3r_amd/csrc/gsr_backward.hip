@@ -313,9 +313,8 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(GsrDims d, const GsrView
 
             // ---- colour ----
             if (DEG >= 0) {
-                float ddx = m[0] - vw.campos[0], ddy = m[1] - vw.campos[1], ddz = m[2] - vw.campos[2];
-                float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz);
-                float x = ddx / len, y = ddy / len, z = ddz / len;
+                float x, y, z, len;
+                sh_view_dir(m, vw.campos, x, y, z, len);
                 float bs[NC];
                 sh_basis(DEG < 0 ? 0 : DEG, x, y, z, bs);
                 float gcol[3];
@@ -493,9 +492,6 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(GsrDims d, const GsrView
 #pragma clang fp contract(fast)
 
 // ------------------------------------------------------------------ host
-int layout(const GsrDims &d, long long cap, GsrLayout &L);
-Ptrs carve(void *base, const GsrLayout &L);
-
 int backward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *shs,
              long long cap, void *workspace, size_t workspace_bytes, const float *dL_dimage, const float *dL_ddepth,
              float *dL_dmeans, float *dL_dcov6, float *dL_dopac, float *dL_dshs, float *dL_dmeans2D, float *dL_dtau,
@@ -528,17 +524,10 @@ int backward(const GsrDims &d, const GsrView *views, const float *means, const f
     }
     tm.end(GSR_STAGE_COMPOSITE_BWD); tm.begin(GSR_STAGE_PREPROCESS_BWD);
     const dim3 gG((d.G + 255) / 256, d.B);
-#define GSR_LAUNCH_K7(DEG) hipLaunchKernelGGL(k_preprocess_bwd<DEG>, gG, dim3(256), 0, stream, d, views, means, cov6, shs, ws, \
-                                              dL_dmeans, dL_dcov6, dL_dopac, dL_dshs, dL_dmeans2D, dL_dtau)
-    switch (d.M > 0 ? d.sh_degree : -1) {
-        case -1: GSR_LAUNCH_K7(-1); break;
-        case 0: GSR_LAUNCH_K7(0); break;
-        case 1: GSR_LAUNCH_K7(1); break;
-        case 2: GSR_LAUNCH_K7(2); break;
-        case 3: GSR_LAUNCH_K7(3); break;
-        default: GSR_LAUNCH_K7(4); break;
-    }
-#undef GSR_LAUNCH_K7
+    with_sh_degree(d, [&](auto deg) {
+        hipLaunchKernelGGL(k_preprocess_bwd<decltype(deg)::value>, gG, dim3(256), 0, stream, d, views, means, cov6, shs, ws, dL_dmeans, dL_dcov6,
+                           dL_dopac, dL_dshs, dL_dmeans2D, dL_dtau);
+    });
     tm.end(GSR_STAGE_PREPROCESS_BWD);
     return launch_status();
 }

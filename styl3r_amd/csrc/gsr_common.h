@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/gsr.h"
 
 namespace gsr {
@@ -96,6 +98,37 @@ struct StageTimer {
     void begin(int stage) { if (slot >= 0 && ((p->mask >> stage) & 1u)) (void)hipEventRecord(p->at(slot, stage, 0), s); }
     void end(int stage) { if (slot >= 0 && ((p->mask >> stage) & 1u)) (void)hipEventRecord(p->at(slot, stage, 1), s); }
 };
+
+// ---- the library's internal interface: gsr_forward.hip (layout, carve, forward), gsr_backward.hip, gsr_styles.hip ----
+int layout(const GsrDims &d, long long cap, GsrLayout &L);
+Ptrs carve(void *base, const GsrLayout &L);
+int forward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *opac,
+            const float *shs, long long cap, void *workspace, size_t workspace_bytes, float *image, float *depth,
+            float *opacity, int32_t *radii, int32_t *n_touched, int32_t *status, const GsrFused *fx, hipStream_t stream,
+            bool composite = true);
+int backward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *shs,
+             long long cap, void *workspace, size_t workspace_bytes, const float *dL_dimage, const float *dL_ddepth,
+             float *dL_dmeans, float *dL_dcov6, float *dL_dopac, float *dL_dshs, float *dL_dmeans2D, float *dL_dtau,
+             const GsrFused *fx, hipStream_t stream);
+int forward_styles(const GsrDims &d, int S, const GsrView *views, const float *means, const float *cov6, const float *opac,
+                   const float *const *shs, long long cap, void *workspace, size_t workspace_bytes, void *extra, size_t extra_bytes,
+                   uint32_t *tile_count, float *image, float *depth, float *opacity, int32_t *radii, int32_t *status, hipStream_t stream);
+
+inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// f(std::integral_constant<int, DEG>) with DEG the compile-time form of the launch's SH degree: 0..4, or -1 for precomputed colours (M = 0)
+template <class F>
+inline void with_sh_degree(const GsrDims &d, F &&f)
+{
+    switch (d.M > 0 ? d.sh_degree : -1) {
+        case -1: f(std::integral_constant<int, -1>{}); break;
+        case 0: f(std::integral_constant<int, 0>{}); break;
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 3: f(std::integral_constant<int, 3>{}); break;
+        default: f(std::integral_constant<int, 4>{}); break;
+    }
+}
 
 __host__ __device__ inline int tiles_x(int W) { return (W + TILE - 1) / TILE; }
 __host__ __device__ inline int tiles_y(int H) { return (H + TILE - 1) / TILE; }
@@ -202,6 +235,35 @@ __device__ inline void sh_basis_grad(int deg, float x, float y, float z, float *
     dx[22] = SH_C4_6 * (2.0f * x) * (7.0f * zz - 1.0f); dy[22] = SH_C4_6 * (-2.0f * y) * (7.0f * zz - 1.0f); dz[22] = SH_C4_6 * (xx - yy) * (14.0f * z);
     dx[23] = SH_C4_7 * z * (3.0f * xx - 3.0f * yy); dy[23] = SH_C4_7 * (-6.0f * xy * z); dz[23] = SH_C4_7 * x * (xx - 3.0f * yy);
     dx[24] = SH_C4_8 * (4.0f * xx * x - 12.0f * x * yy); dy[24] = SH_C4_8 * (-12.0f * xx * y + 4.0f * yy * y); dz[24] = 0.f;
+}
+
+// unit direction from the camera to the (scaled) mean `m`, and its length
+__device__ __forceinline__ void sh_view_dir(const float *m, const float *campos, float &x, float &y, float &z, float &len)
+{
+    float dx = m[0] - campos[0], dy = m[1] - campos[1], dz = m[2] - campos[2];
+    len = sqrtf(dx * dx + dy * dy + dz * dz);
+    x = dx / len; y = dy / len; z = dz / len;
+}
+
+// colour of one Gaussian seen along (x, y, z) from its coefficients sh[k][3]: the ordered sum over the (DEG + 1)^2 basis functions, + 0.5,
+// clamped at 0.  Returns bit c set where channel c was clamped (its gradient is zero).
+template <int DEG>
+__device__ __forceinline__ uint32_t sh_colour(float x, float y, float z, const float *__restrict__ sh, float *col)
+{
+    constexpr int NC = (DEG + 1) * (DEG + 1);
+    float bs[NC];
+    sh_basis(DEG, x, y, z, bs);
+    uint32_t clampbits = 0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float acc = bs[0] * sh[c];
+#pragma unroll
+        for (int k = 1; k < NC; ++k) acc = acc + bs[k] * sh[3 * k + c];
+        acc = acc + 0.5f;
+        if (acc < 0.f) clampbits |= (1u << c);
+        col[c] = fmaxf(acc, 0.f);
+    }
+    return clampbits;
 }
 
 // Camera-space geometry of one Gaussian (mirrors gso_geom_eval of the oracle
@@ -386,6 +448,14 @@ __device__ inline float wave_sum_to_lane63(float v)
     v += dpp_mov<0x128, 0xf, 0xf, true>(v);  // row_ror:8  (every lane of a row now holds the row sum)
     v += dpp_mov<0x142, 0xa, 0xf, false>(v); // row_bcast:15 -> rows 1,3
     v += dpp_mov<0x143, 0xc, 0xf, false>(v); // row_bcast:31 -> rows 2,3
+    return v;
+}
+
+// sum of a double over the 64 lanes (xor butterfly: the same value, in the same order, in every lane)
+__device__ inline double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
 

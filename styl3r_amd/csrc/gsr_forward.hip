@@ -58,7 +58,6 @@ __global__ void __launch_bounds__(256) k_preprocess(GsrDims d, const GsrView *__
     load_cov(cov6, sg, (d.flags & GSR_FLAG_COV9) != 0, S0);
     const float op = opac[sg];
     const int gx = tiles_x(d.W), gy = tiles_y(d.H), T = gx * gy;
-    constexpr int NC = DEG < 0 ? 1 : (DEG + 1) * (DEG + 1);
     if (lds_tiles) {
         for (int t = threadIdx.x; t < T; t += 256) s_tiles[t] = 0u;
         __syncthreads();
@@ -105,23 +104,10 @@ __global__ void __launch_bounds__(256) k_preprocess(GsrDims d, const GsrView *__
             }
         }
         if (ok) {
-            if (DEG >= 0) {
-                float dx = m[0] - vw.campos[0], dy = m[1] - vw.campos[1], dz = m[2] - vw.campos[2];
-                float len = sqrtf(dx * dx + dy * dy + dz * dz);
-                float x = dx / len, y = dy / len, z = dz / len;
-                float bs[NC];
-                sh_basis(DEG < 0 ? 0 : DEG, x, y, z, bs);
-                const float *sh = shs + sg * 3 * (size_t)d.M;
-                float col[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    float acc = bs[0] * sh[c];
-#pragma unroll
-                    for (int k = 1; k < NC; ++k) acc = acc + bs[k] * sh[3 * k + c];
-                    acc = acc + 0.5f;
-                    if (acc < 0.f) clampbits |= (1u << c);
-                    col[c] = fmaxf(acc, 0.f);
-                }
+            if constexpr (DEG >= 0) {
+                float x, y, z, len, col[3];
+                sh_view_dir(m, vw.campos, x, y, z, len);
+                clampbits = sh_colour<DEG>(x, y, z, shs + sg * 3 * (size_t)d.M, col);
                 rec.r = col[0]; rec.g = col[1]; rec.b = col[2];
             } else {
                 rec.r = shs[3 * sg]; rec.g = shs[3 * sg + 1]; rec.b = shs[3 * sg + 2];
@@ -904,8 +890,6 @@ __global__ void __launch_bounds__(64) k_composite_fwd(GsrDims d, const GsrView *
 }
 
 // ------------------------------------------------------------------ host
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
-
 int layout(const GsrDims &d, long long cap, GsrLayout &L)
 {
     if (d.B <= 0 || d.Vt <= 0 || d.G <= 0 || d.H <= 0 || d.W <= 0 || cap <= 0) return GSR_EINVAL;
@@ -1000,16 +984,9 @@ int forward(const GsrDims &d, const GsrView *views, const float *means, const fl
     if (ntouch && !hip_ok(hipMemsetAsync(n_touched, 0, (size_t)V * d.G * 4, stream))) return GSR_ELAUNCH;
 
     tm.begin(GSR_STAGE_PREPROCESS);
-#define GSR_LAUNCH_K1(DEG) hipLaunchKernelGGL(k_preprocess<DEG>, gG, dim3(256), lds_tiles * 4, stream, d, views, means, cov6, opac, shs, ws, radii, lds_tiles)
-    switch (d.M > 0 ? d.sh_degree : -1) {
-        case -1: GSR_LAUNCH_K1(-1); break;
-        case 0: GSR_LAUNCH_K1(0); break;
-        case 1: GSR_LAUNCH_K1(1); break;
-        case 2: GSR_LAUNCH_K1(2); break;
-        case 3: GSR_LAUNCH_K1(3); break;
-        default: GSR_LAUNCH_K1(4); break;
-    }
-#undef GSR_LAUNCH_K1
+    with_sh_degree(d, [&](auto deg) {
+        hipLaunchKernelGGL(k_preprocess<decltype(deg)::value>, gG, dim3(256), lds_tiles * 4, stream, d, views, means, cov6, opac, shs, ws, radii, lds_tiles);
+    });
     tm.end(GSR_STAGE_PREPROCESS); tm.begin(GSR_STAGE_SCAN);
     {
         const uint32_t seg = seg_len(d);

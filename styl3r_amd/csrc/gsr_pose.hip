@@ -21,12 +21,11 @@
 //   6. k_pnp_finish   inlier mask and count under the final pose in float64, c2w = (R|t)^-1.
 //   Failure (fewer than 6 masked points, no valid hypothesis) is a status code and the identity pose.
 //
-// gsr_ssim_structure_fwd / _bwd: `1 - structure` of src/loss/loss_ssim.py:80-124 (data_range 1, K = (0.01, 0.03), valid 11 x 11 window,
-//   compensation 1, eps^2 / min / 0.98 clamps) with the tiling of k_image_scores (gsr_metrics.hip): one wave per (plane, strip of 64 columns,
-//   chunk of 32 rows), rows staged through LDS, an 11-row register ring, moments of the images shifted by the tile's first pixel (summed in
-//   float64, kept in fp32; the window's sum differs from 1 in fp32 and the shift is corrected for it).  The
-//   forward optionally leaves the three per-pixel adjoint maps (d/d mu2, d/d E[y^2], d/d E[xy]); the backward is the same walk over those
-//   maps, zero-padded by 10 on every side (the transposed filter), combined with the pixel's own x and y.
+// gsr_pose_adam_update: the pose step of test_step_align (src/model/model_wrapper_style.py:430-440) for n views in one launch -- Adam
+//   (torch.optim.Adam defaults, two parameter groups) on the zero deltas, then w2c' = SE3_exp(trans, rot) w2c
+//   (src/misc/cam_utils.py:67-137), c2w' = w2c'^-1.
+//
+// (The SSIM structure term the refinement loop minimises is in gsr_ssim.hip.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -58,20 +57,18 @@ struct PnpLayout {
     int granules, blocks;
 };
 
-static size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 static PnpLayout pnp_layout(int64_t P, int64_t N, int iterations)
 {
     PnpLayout L;
     L.granules = (int)((N + PNP_GRANULE - 1) / PNP_GRANULE);
     L.blocks = (int)((N + PNP_BLOCK_POINTS - 1) / PNP_BLOCK_POINTS);
     size_t o = 0;
-    L.prefix = o; o = align256(o + (size_t)P * (L.granules + 1) * sizeof(int32_t));
-    L.counts = o; o = align256(o + (size_t)P * iterations * sizeof(int32_t));
-    L.valid = o; o = align256(o + (size_t)P * iterations * sizeof(int32_t));
-    L.hypo = o; o = align256(o + (size_t)P * iterations * 12 * sizeof(double));
-    L.state = o; o = align256(o + (size_t)P * PNP_STATE * sizeof(double));
-    L.partial = o; o = align256(o + (size_t)P * L.blocks * PNP_TERMS_PAD * sizeof(double));
+    L.prefix = o; o = align_up(o + (size_t)P * (L.granules + 1) * sizeof(int32_t), 256);
+    L.counts = o; o = align_up(o + (size_t)P * iterations * sizeof(int32_t), 256);
+    L.valid = o; o = align_up(o + (size_t)P * iterations * sizeof(int32_t), 256);
+    L.hypo = o; o = align_up(o + (size_t)P * iterations * 12 * sizeof(double), 256);
+    L.state = o; o = align_up(o + (size_t)P * PNP_STATE * sizeof(double), 256);
+    L.partial = o; o = align_up(o + (size_t)P * L.blocks * PNP_TERMS_PAD * sizeof(double), 256);
     L.total = o;
     return L;
 }
@@ -458,13 +455,6 @@ __global__ void __launch_bounds__(64) k_pnp_select(PnpArgs a, int P)
     a.status[4 * p + 3] = code;
 }
 
-__device__ inline double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // ---- 5a. normal equations and truncated cost of the candidate pose, per block ----
 __global__ void __launch_bounds__(PNP_THREADS) k_pnp_accum(PnpArgs a)
 {
@@ -582,202 +572,106 @@ __global__ void __launch_bounds__(PNP_THREADS) k_pnp_finish(PnpArgs a)
 }
 
 // ======================================================================================================================
-// SSIM structure term
+// Pose step: one thread per view
 // ======================================================================================================================
-constexpr int SS_COLS = 64;
-constexpr int SS_ROWS = 32;
-constexpr int SS_R = 5;
-constexpr int SS_WIN = 2 * SS_R + 1;
-constexpr int SS_IN = SS_COLS + 2 * SS_R;
-constexpr float SS_C3 = 0.5f * (0.03f * 0.03f);                       // C2 / 2, C2 = (K2 data_range)^2
-constexpr float SS_EPS2 = 1.1920928955078125e-07f * 1.1920928955078125e-07f;   // finfo(float32).eps^2
-constexpr float SS_CLAMP = 0.98f;
-
-struct Window {
-    float w[SS_WIN];
-};
-
-__global__ void __launch_bounds__(64) k_ssim_struct_fwd(const float *__restrict__ gt, const float *__restrict__ pred, int H, int W, int strips,
-                                                        int chunks, Window win, double wsum2, double *__restrict__ partial,
-                                                        float *__restrict__ maps, size_t map_stride)
+__device__ inline void inverse4_f64(const double *m, double *inv)
 {
-    __shared__ float sx[2][SS_IN], sy[2][SS_IN];
-    const int lane = threadIdx.x;
-    const int tiles = strips * chunks;
-    const long long blk = blockIdx.x;
-    const long long plane = blk / tiles;
-    const int t = (int)(blk - plane * tiles);
-    const int k = t / strips, s = t - k * strips;
-    const int Ho = H - 2 * SS_R, Wo = W - 2 * SS_R;
-    const int c0 = s * SS_COLS;
-    const int r0 = k * SS_ROWS, r1 = min(r0 + SS_ROWS, Ho) + 2 * SS_R;    // input rows [r0, r1)
-    const float *X = gt + (size_t)plane * H * W, *Y = pred + (size_t)plane * H * W;
-    const float kx = X[(size_t)r0 * W + c0], ky = Y[(size_t)r0 * W + c0];
-    const int cm = c0 + lane, ch = c0 + SS_COLS + lane;
-    const bool in_m = cm < W, in_h = lane < 2 * SS_R && ch < W;
-    const bool out_col = cm < Wo;
-
-    float xm = 0.f, ym = 0.f, xh = 0.f, yh = 0.f;
-    auto load_row = [&](int r) {
-        const size_t o = (size_t)r * W;
-        xm = in_m ? X[o + cm] : 0.f; ym = in_m ? Y[o + cm] : 0.f;
-        xh = in_h ? X[o + ch] : 0.f; yh = in_h ? Y[o + ch] : 0.f;
-    };
-    load_row(r0);
-
-    float ring[SS_WIN][5];
-    double acc = 0.0;
-    for (int rb = r0; rb < r1; rb += SS_WIN) {
+    // Gauss-Jordan with partial pivoting on [m | I] (row-major): the general inverse of update_pose's `extrinsics.inverse()`
+    double a[4][8];
 #pragma unroll
-        for (int j = 0; j < SS_WIN; ++j) {
-            const int r = rb + j;
-            if (r >= r1) continue;
-            const int b = (r - r0) & 1;
-            sx[b][lane] = xm - kx; sy[b][lane] = ym - ky;
-            if (lane < 2 * SS_R) { sx[b][SS_COLS + lane] = xh - kx; sy[b][SS_COLS + lane] = yh - ky; }
-            if (r + 1 < r1) load_row(r + 1);
-            __syncthreads();
-            // float64 sums (the products of fp32 values are exact in it), fp32 ring: the variances are differences of these sums
-            double h0 = 0.0, h1 = 0.0, h2 = 0.0, h3 = 0.0, h4 = 0.0;
+    for (int r = 0; r < 4; ++r)
 #pragma unroll
-            for (int q = 0; q < SS_WIN; ++q) {
-                const double av = (double)sx[b][lane + q], cv = (double)sy[b][lane + q], wa = (double)win.w[q] * av, wc = (double)win.w[q] * cv;
-                h0 += wa; h1 += wc; h2 += wa * av; h3 += wc * cv; h4 += wa * cv;
+        for (int c = 0; c < 4; ++c) { a[r][c] = m[4 * r + c]; a[r][4 + c] = (r == c) ? 1.0 : 0.0; }
+#pragma unroll
+    for (int col = 0; col < 4; ++col) {
+        int piv = col;
+        double best = fabs(a[col][col]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r > col && fabs(a[r][col]) > best) { best = fabs(a[r][col]); piv = r; }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (r == piv && piv != col) {
+#pragma unroll
+                for (int c = 0; c < 8; ++c) { const double t = a[col][c]; a[col][c] = a[r][c]; a[r][c] = t; }
             }
-            ring[j][0] = (float)h0; ring[j][1] = (float)h1; ring[j][2] = (float)h2; ring[j][3] = (float)h3; ring[j][4] = (float)h4;
-            if (r - r0 >= 2 * SS_R && out_col) {
-                double m0 = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0, m4 = 0.0;
+        const double d = 1.0 / a[col][col];
 #pragma unroll
-                for (int i = 0; i < SS_WIN; ++i) {
-                    const int sl = (j + 1 + i) % SS_WIN;
-                    const double w = (double)win.w[i];
-                    m0 += w * (double)ring[sl][0]; m1 += w * (double)ring[sl][1]; m2 += w * (double)ring[sl][2];
-                    m3 += w * (double)ring[sl][3]; m4 += w * (double)ring[sl][4];
-                }
-                // The fp32-normalised taps do not sum to 1 exactly (wsum2 = (sum w)^2 over the 11 x 11 window), so variances are NOT
-                // invariant under the shift: sum w x^2 - (sum w x)^2 = m2 - m0^2 + (1 - wsum2) (2 kx m0 + kx^2 wsum2) for x = a + kx.
-                const double oms = 1.0 - wsum2, dkx = (double)kx, dky = (double)ky;
-                const float s1 = (float)(m2 - m0 * m0 + oms * (2.0 * dkx * m0 + dkx * dkx * wsum2));
-                const float s2 = (float)(m3 - m1 * m1 + oms * (2.0 * dky * m1 + dky * dky * wsum2));
-                const float c = (float)(m4 - m0 * m1 + oms * (dkx * m1 + dky * m0 + dkx * dky * wsum2));
-                const float ux = (float)(m0 + dkx * wsum2), uy = (float)(m1 + dky * wsum2);      // sum w x, sum w y
-                const float v1 = fmaxf(s1, SS_EPS2), v2 = fmaxf(s2, SS_EPS2);
-                const float pr = sqrtf(v1 * v2), ac = fabsf(c);
-                const bool capped = ac > pr;
-                const float cp = capped ? copysignf(pr, c) : c;
-                const float q1 = sqrtf(v1), q2 = sqrtf(v2);
-                const float D = q1 * q2 + SS_C3;
-                const float sv = (cp + SS_C3) / D;
-                const bool clamped = sv > SS_CLAMP;
-                acc += (double)(clamped ? SS_CLAMP : sv);
-                if (maps) {
-                    float a_mu = 0.f, a_yy = 0.f, a_c = 0.f;
-                    if (!clamped) {
-                        const float invD = 1.f / D;
-                        a_c = capped ? 0.f : invD;
-                        float dv2 = -(sv * invD) * (q1 / (2.f * q2));
-                        if (capped) dv2 += copysignf(invD, c) * (v1 / (2.f * pr));
-                        a_yy = (s2 < SS_EPS2) ? 0.f : dv2;
-                        a_mu = -2.f * uy * a_yy - ux * a_c;
-                    }
-                    const size_t o = ((size_t)plane * Ho + (r - 2 * SS_R)) * Wo + cm;
-                    maps[o] = a_mu; maps[map_stride + o] = a_yy; maps[2 * map_stride + o] = a_c;
-                }
-            }
+        for (int c = 0; c < 8; ++c) a[col][c] *= d;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (r == col) continue;
+            const double f = a[r][col];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) a[r][c] -= f * a[col][c];
         }
     }
-    acc = wave_sum(acc);
-    if (lane == 0) partial[blk] = acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) inv[4 * r + c] = a[r][4 + c];
 }
 
-// one wave per image: its C * tiles partials in index order
-__global__ void __launch_bounds__(64) k_ssim_struct_fold(const double *__restrict__ partial, int per_image, double inv, float *__restrict__ out)
+__global__ void __launch_bounds__(64) k_pose_adam(float *__restrict__ c2w, float *__restrict__ m, float *__restrict__ v,
+                                                  const float *__restrict__ grad_rot, const float *__restrict__ grad_trans, long long n,
+                                                  float step_rot, float step_trans, float beta1, float beta2, float eps, float bc2_sqrt)
 {
-    const long long n = blockIdx.x;
-    const double *p = partial + n * per_image;
-    double s = 0.0;
-    for (int i = threadIdx.x; i < per_image; i += 64) s += p[i];
-    s = wave_sum(s);
-    if (threadIdx.x == 0) out[n] = (float)(s * inv);
-}
-
-// one wave per (plane, strip of 64 image columns, chunk of 32 image rows): the valid filter of the adjoint maps padded with 10 zeros
-__global__ void __launch_bounds__(64) k_ssim_struct_bwd(const float *__restrict__ gt, const float *__restrict__ pred,
-                                                        const float *__restrict__ maps, size_t map_stride, const float *__restrict__ grad_out,
-                                                        float inv_norm, int C, int H, int W, int strips, int chunks, Window win,
-                                                        float *__restrict__ grad)
-{
-    __shared__ float sm[2][3][SS_IN];
-    const int lane = threadIdx.x;
-    const int tiles = strips * chunks;
-    const long long blk = blockIdx.x;
-    const long long plane = blk / tiles;
-    const int t = (int)(blk - plane * tiles);
-    const int k = t / strips, s = t - k * strips;
-    const int Ho = H - 2 * SS_R, Wo = W - 2 * SS_R;
-    const int c0 = s * SS_COLS;
-    const int r0 = k * SS_ROWS, r1 = min(r0 + SS_ROWS, H);                 // image rows [r0, r1)
-    const int m0 = r0 - 2 * SS_R;                                          // first (virtual) map row of the walk
-    const float *X = gt + (size_t)plane * H * W, *Y = pred + (size_t)plane * H * W;
-    const float *A0 = maps + (size_t)plane * Ho * Wo, *A1 = A0 + map_stride, *A2 = A1 + map_stride;
-    const float scale = grad_out[plane / C] * inv_norm;
-    const int mc = c0 - 2 * SS_R + lane, hc = c0 + SS_COLS - 2 * SS_R + lane;
-    const bool in_m = mc >= 0 && mc < Wo, in_h = lane < 2 * SS_R && hc < Wo;
-    const int ci = c0 + lane;
-
-    float am[3] = {0.f, 0.f, 0.f}, ah[3] = {0.f, 0.f, 0.f};
-    auto load_row = [&](int m) {
-        const bool row = m >= 0 && m < Ho;                                  // (uniform)
-        const size_t o = (size_t)(row ? m : 0) * Wo;
-        am[0] = row && in_m ? A0[o + mc] : 0.f; am[1] = row && in_m ? A1[o + mc] : 0.f; am[2] = row && in_m ? A2[o + mc] : 0.f;
-        ah[0] = row && in_h ? A0[o + hc] : 0.f; ah[1] = row && in_h ? A1[o + hc] : 0.f; ah[2] = row && in_h ? A2[o + hc] : 0.f;
-    };
-    load_row(m0);
-
-    float ring[SS_WIN][3];
-    for (int mb = m0; mb < r1; mb += SS_WIN) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    // Adam on a parameter that is 0 before every step (the reference resets the deltas): theta = -step_size * m / denom, with
+    // torch's fp32 arithmetic (exp_avg.lerp_, exp_avg_sq.mul_().addcmul_(), sqrt / bc2_sqrt + eps, addcdiv_)
+    double d[6];                                   // (rot, trans) -> tau = (rho = trans, theta = rot) below
 #pragma unroll
-        for (int j = 0; j < SS_WIN; ++j) {
-            const int m = mb + j;
-            if (m >= r1) continue;
-            const int b = (m - m0) & 1;
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                sm[b][q][lane] = am[q];
-                if (lane < 2 * SS_R) sm[b][q][SS_COLS + lane] = ah[q];
-            }
-            if (m + 1 < r1) load_row(m + 1);
-            __syncthreads();
-            float h0 = 0.f, h1 = 0.f, h2 = 0.f;
-#pragma unroll
-            for (int q = 0; q < SS_WIN; ++q) {
-                const float w = win.w[SS_WIN - 1 - q];
-                h0 += w * sm[b][0][lane + q]; h1 += w * sm[b][1][lane + q]; h2 += w * sm[b][2][lane + q];
-            }
-            ring[j][0] = h0; ring[j][1] = h1; ring[j][2] = h2;
-            if (m >= r0 && ci < W) {                                        // map rows m-10 .. m are in slots j+1 .. j (mod 11)
-                float v0 = 0.f, v1 = 0.f, v2 = 0.f;
-#pragma unroll
-                for (int i = 0; i < SS_WIN; ++i) {
-                    const int sl = (j + 1 + i) % SS_WIN;
-                    const float w = win.w[SS_WIN - 1 - i];
-                    v0 += w * ring[sl][0]; v1 += w * ring[sl][1]; v2 += w * ring[sl][2];
-                }
-                const size_t o = (size_t)m * W + ci;
-                grad[(size_t)plane * H * W + o] = scale * (v0 + 2.f * Y[o] * v1 + X[o] * v2);
-            }
-        }
+    for (int q = 0; q < 6; ++q) {
+        const float g = q < 3 ? grad_rot[3 * i + q] : grad_trans[3 * i + q - 3];
+        float mq = m[6 * i + q], vq = v[6 * i + q];
+        mq = mq + (1.f - beta1) * (g - mq);
+        vq = vq * beta2 + (1.f - beta2) * g * g;
+        m[6 * i + q] = mq; v[6 * i + q] = vq;
+        const float denom = sqrtf(vq) / bc2_sqrt + eps;
+        d[q] = (double)(-(q < 3 ? step_rot : step_trans) * (mq / denom));
     }
-}
-
-static bool ssim_grid(int64_t N, int C, int H, int W, bool image_rows, int &strips, int &chunks, long long &blocks)
-{
-    if (N < 1 || C < 1 || H < SS_WIN || W < SS_WIN) return false;
-    const int cols = image_rows ? W : W - 2 * SS_R, rows = image_rows ? H : H - 2 * SS_R;
-    strips = (cols + SS_COLS - 1) / SS_COLS;
-    chunks = (rows + SS_ROWS - 1) / SS_ROWS;
-    blocks = (long long)N * C * strips * chunks;
-    return blocks <= 0x7fffffffLL && (long long)N * C * H * W <= 0x7fffffffffLL;
+    const double th[3] = {d[0], d[1], d[2]}, rho[3] = {d[3], d[4], d[5]};
+    // SE3_exp (cam_utils.py:67-116): W = [theta]x, R = SO3_exp(theta), t = V(theta) rho
+    const double Wm[3][3] = {{0.0, -th[2], th[1]}, {th[2], 0.0, -th[0]}, {-th[1], th[0], 0.0}};
+    double W2[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) W2[r][c] = Wm[r][0] * Wm[0][c] + Wm[r][1] * Wm[1][c] + Wm[r][2] * Wm[2][c];
+    const double angle = sqrt(th[0] * th[0] + th[1] * th[1] + th[2] * th[2]);
+    double rw, rw2, vw, vw2;
+    if (angle < 1e-5) { rw = 1.0; rw2 = 0.5; vw = 0.5; vw2 = 1.0 / 6.0; }
+    else {
+        const double a2 = angle * angle;
+        rw = sin(angle) / angle; rw2 = (1.0 - cos(angle)) / a2;
+        vw = rw2; vw2 = (angle - sin(angle)) / (a2 * angle);
+    }
+    double T[16];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double t = 0.0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double id = r == c ? 1.0 : 0.0;
+            T[4 * r + c] = id + rw * Wm[r][c] + rw2 * W2[r][c];
+            t += (id + vw * Wm[r][c] + vw2 * W2[r][c]) * rho[c];
+        }
+        T[4 * r + 3] = t;
+    }
+    T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+    double E[16], w2c[16], nw[16], out[16];
+#pragma unroll
+    for (int q = 0; q < 16; ++q) E[q] = (double)c2w[16 * i + q];
+    inverse4_f64(E, w2c);
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            nw[4 * r + c] = T[4 * r] * w2c[c] + T[4 * r + 1] * w2c[4 + c] + T[4 * r + 2] * w2c[8 + c] + T[4 * r + 3] * w2c[12 + c];
+    inverse4_f64(nw, out);
+#pragma unroll
+    for (int q = 0; q < 16; ++q) c2w[16 * i + q] = (float)out[q];
 }
 
 }  // namespace pe
@@ -829,50 +723,16 @@ __attribute__((visibility("default"))) int gsr_pnp_ransac(const float *pts3d, co
     return gsr::launch_status();
 }
 
-__attribute__((visibility("default"))) size_t gsr_ssim_structure_scratch_bytes(int64_t N, int C, int H, int W)
+__attribute__((visibility("default"))) int gsr_pose_adam_update(float *c2w, float *m, float *v, const float *grad_rot, const float *grad_trans,
+                                                                int64_t n, int step, float lr_rot, float lr_trans, float beta1, float beta2,
+                                                                float eps, void *stream)
 {
-    int strips, chunks;
-    long long blocks;
-    if (!ssim_grid(N, C, H, W, false, strips, chunks, blocks)) return 0;
-    return (size_t)blocks * sizeof(double);
-}
-
-__attribute__((visibility("default"))) int gsr_ssim_structure_fwd(const float *target, const float *pred, int64_t N, int C, int H, int W,
-                                                                  const float *window, float *structure, float *maps, void *scratch,
-                                                                  void *stream)
-{
-    int strips, chunks;
-    long long blocks;
-    if (!target || !pred || !window || !structure || !scratch || !ssim_grid(N, C, H, W, false, strips, chunks, blocks)) return GSR_EINVAL;
-    Window win;
-    double wsum = 0.0;
-    for (int q = 0; q < SS_WIN; ++q) { win.w[q] = window[q]; wsum += (double)window[q]; }
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    double *partial = static_cast<double *>(scratch);
-    const size_t map_stride = (size_t)N * C * (H - 2 * SS_R) * (W - 2 * SS_R);
+    if (!c2w || !m || !v || !grad_rot || !grad_trans || n < 1 || step < 1) return GSR_EINVAL;
+    // torch.optim.Adam (capturable=False): the bias corrections and the step size are host doubles, used by the fp32 kernel as floats
+    const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
     (void)hipGetLastError();
-    hipLaunchKernelGGL(k_ssim_struct_fwd, dim3((unsigned)blocks), dim3(64), 0, st, target, pred, H, W, strips, chunks, win, wsum * wsum, partial,
-                       maps, map_stride);
-    const double inv = 1.0 / ((double)C * (H - 2 * SS_R) * (W - 2 * SS_R));
-    hipLaunchKernelGGL(k_ssim_struct_fold, dim3((unsigned)N), dim3(64), 0, st, partial, C * strips * chunks, inv, structure);
-    return gsr::launch_status();
-}
-
-__attribute__((visibility("default"))) int gsr_ssim_structure_bwd(const float *target, const float *pred, const float *maps,
-                                                                  const float *grad_structure, int64_t N, int C, int H, int W,
-                                                                  const float *window, float *grad_pred, void *stream)
-{
-    int strips, chunks;
-    long long blocks;
-    if (!target || !pred || !maps || !grad_structure || !window || !grad_pred || !ssim_grid(N, C, H, W, true, strips, chunks, blocks))
-        return GSR_EINVAL;
-    Window win;
-    for (int q = 0; q < SS_WIN; ++q) win.w[q] = window[q];
-    const size_t map_stride = (size_t)N * C * (H - 2 * SS_R) * (W - 2 * SS_R);
-    const float inv_norm = (float)(1.0 / ((double)C * (H - 2 * SS_R) * (W - 2 * SS_R)));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(k_ssim_struct_bwd, dim3((unsigned)blocks), dim3(64), 0, static_cast<hipStream_t>(stream), target, pred, maps, map_stride,
-                       grad_structure, inv_norm, C, H, W, strips, chunks, win, grad_pred);
+    hipLaunchKernelGGL(k_pose_adam, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), c2w, m, v, grad_rot,
+                       grad_trans, (long long)n, (float)(lr_rot / bc1), (float)(lr_trans / bc1), beta1, beta2, eps, (float)sqrt(bc2));
     return gsr::launch_status();
 }
 

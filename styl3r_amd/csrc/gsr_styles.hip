@@ -2,8 +2,8 @@
 // only in colour go through ONE preprocess / tile scan / scatter / per-tile sort (the kernels of gsr_forward.hip, unchanged) and are
 // shaded together.
 //
-//   K1s style_colours   the colours of styles 1..S-1 (style 0's stay in the SplatRec, written by K1): the SH sum and clamp of
-//                       k_preprocess<DEG>, operation for operation, for splats with radius > 0, into a side array of one float4 per
+//   K1s style_colours   the colours of styles 1..S-1 (style 0's stay in the SplatRec, written by K1): sh_view_dir + sh_colour<DEG> (gsr_common.h),
+//                       the routine k_preprocess<DEG> calls, for splats with radius > 0, into a side array of one float4 per
 //                       (style, view, Gaussian) -- or per (style, scene, Gaussian) at degree 0 / precomputed RGB, where the colour
 //                       does not depend on the view.
 //   K5s composite_fwd_styles<NS, FIRST>
@@ -18,13 +18,6 @@
 #include "gsr_common.h"
 
 namespace gsr {
-int layout(const GsrDims &d, long long cap, GsrLayout &L);
-Ptrs carve(void *base, const GsrLayout &L);
-int forward(const GsrDims &d, const GsrView *views, const float *means, const float *cov6, const float *opac,
-            const float *shs, long long cap, void *workspace, size_t workspace_bytes, float *image, float *depth,
-            float *opacity, int32_t *radii, int32_t *n_touched, int32_t *status, const GsrFused *fx, hipStream_t stream,
-            bool composite);
-
 constexpr int STYLES_PER_LAUNCH = 4;    // styles one composite launch shades (register budget: DESIGN R10)
 constexpr int COLOUR_PTRS = 8;          // SH tensors one launch of the colour kernel serves (grid z)
 struct ColourSrc { const float *shs[COLOUR_PTRS]; };
@@ -43,7 +36,6 @@ __global__ void __launch_bounds__(256) k_style_colours(GsrDims d, const GsrView 
     if (g >= d.G) return;
     const float *__restrict__ shs = src.shs[blockIdx.z];
     float4 *__restrict__ dst = side + (size_t)blockIdx.z * style_stride + (size_t)blockIdx.y * d.G + g;
-    constexpr int NC = DEG < 0 ? 1 : (DEG + 1) * (DEG + 1);
     if (DEG <= 0) {      // blockIdx.y = scene
         const size_t sg = (size_t)blockIdx.y * d.G + g;
         float col[3];
@@ -67,21 +59,9 @@ __global__ void __launch_bounds__(256) k_style_colours(GsrDims d, const GsrView 
     const GsrView &vw = views[v];
     const float s = vw.scale;
     const float m[3] = {means[3 * sg] * s, means[3 * sg + 1] * s, means[3 * sg + 2] * s};
-    float dx = m[0] - vw.campos[0], dy = m[1] - vw.campos[1], dz = m[2] - vw.campos[2];
-    float len = sqrtf(dx * dx + dy * dy + dz * dz);
-    float x = dx / len, y = dy / len, z = dz / len;
-    float bs[NC];
-    sh_basis(DEG < 0 ? 0 : DEG, x, y, z, bs);
-    const float *sh = shs + sg * 3 * (size_t)d.M;
-    float col[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        float acc = bs[0] * sh[c];
-#pragma unroll
-        for (int k = 1; k < NC; ++k) acc = acc + bs[k] * sh[3 * k + c];
-        acc = acc + 0.5f;
-        col[c] = fmaxf(acc, 0.f);
-    }
+    float x, y, z, len, col[3];
+    sh_view_dir(m, vw.campos, x, y, z, len);
+    sh_colour<(DEG < 0 ? 0 : DEG)>(x, y, z, shs + sg * 3 * (size_t)d.M, col);      // (the clamp bits are the backward's: unused here)
     *dst = make_float4(col[0], col[1], col[2], 0.f);
 }
 #pragma clang fp contract(fast)
@@ -267,16 +247,9 @@ int forward_styles(const GsrDims &d, int S, const GsrView *views, const float *m
         for (int i = 0; i < COLOUR_PTRS; ++i) src.shs[i] = shs[s0 + (i < ns ? i : 0)];
         float4 *dst = side + (size_t)(s0 - 1) * side_stride;
         const dim3 grid(cgrid.x, cgrid.y, ns);
-#define GSR_LAUNCH_K1S(DEG) hipLaunchKernelGGL(k_style_colours<DEG>, grid, dim3(256), 0, stream, d, views, means, src, radii, dst, side_stride)
-        switch (d.M > 0 ? d.sh_degree : -1) {
-            case -1: GSR_LAUNCH_K1S(-1); break;
-            case 0: GSR_LAUNCH_K1S(0); break;
-            case 1: GSR_LAUNCH_K1S(1); break;
-            case 2: GSR_LAUNCH_K1S(2); break;
-            case 3: GSR_LAUNCH_K1S(3); break;
-            default: GSR_LAUNCH_K1S(4); break;
-        }
-#undef GSR_LAUNCH_K1S
+        with_sh_degree(d, [&](auto deg) {
+            hipLaunchKernelGGL(k_style_colours<decltype(deg)::value>, grid, dim3(256), 0, stream, d, views, means, src, radii, dst, side_stride);
+        });
     }
 
     // composite: launches of at most `per` styles over the same sorted lists, sizes as even as possible (5 -> 3 + 2, 8 -> 4 + 4)

@@ -1,7 +1,7 @@
 """Image scores of the test step: `compute_psnr`, `compute_ssim`, `compute_lpips` (src/evaluation/metrics.py:11-52), same signatures and
 `(batch,)` results.
 
-fp32 device images go through libgsr_hip.so's `gsr_image_scores` (csrc/gsr_metrics.hip): one pass over both images yields SSIM and the
+fp32 device images go through libgsr_hip.so's `gsr_image_scores` (csrc/gsr_ssim.hip): one pass over both images yields SSIM and the
 clipped mean squared error PSNR is formed from, so `image_scores` returns both from one launch.  Anything else (CPU tensors, other
 dtypes) takes the plain float64 expression of the same formulas, as `losses.mse_loss` does.
 

@@ -9,7 +9,10 @@ import torch
 from tests import metrics_reference as ref
 
 DEV = torch.device("cuda:0")
-SHAPES = [(1, 1, 11, 11), (3, 3, 11, 64), (3, 1, 37, 53), (1, 3, 256, 256), (3, 3, 256, 448), (1, 3, 512, 512), (40, 3, 256, 256)]
+# (1, 1, 42, 74): exactly one full strip and one full chunk (64 x 32 outputs); (1, 1, 43, 75): a second strip and a second chunk that own one
+# output column and one output row each (the last strip's halo and the last chunk's rows of the squared error)
+SHAPES = [(1, 1, 11, 11), (3, 3, 11, 64), (3, 1, 37, 53), (1, 3, 256, 256), (3, 3, 256, 448), (1, 3, 512, 512), (40, 3, 256, 256),
+          (1, 1, 42, 74), (1, 1, 43, 75)]
 CASES = ["random", "identical", "zeros", "out_of_range", "near_identical", "border_only"]
 
 

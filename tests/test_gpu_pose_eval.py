@@ -106,11 +106,13 @@ def _check_structure(tag, x, y):
 
 
 STRUCTURE_SHAPES = [(3, 3, 256, 256), (2, 3, 75, 131), (1, 1, 11, 11)]
+# one full strip x one full chunk of the map, and the same plus a one-column strip and a one-row chunk (2 x 2 tiles in the backward too)
+TILE_EDGE_SHAPES = [(1, 1, 42, 74), (1, 1, 43, 75)]
+STRUCTURE_CASES = [(c, s) for c in ("rendered", "noise") for s in STRUCTURE_SHAPES] + [("noise", s) for s in TILE_EDGE_SHAPES]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("shape", STRUCTURE_SHAPES, ids=lambda s: "x".join(map(str, s)))
-@pytest.mark.parametrize("case", ["rendered", "noise"])
+@pytest.mark.parametrize("case,shape", STRUCTURE_CASES, ids=lambda v: v if isinstance(v, str) else "x".join(map(str, v)))
 def test_ssim_structure_matches_the_float64_expression(case, shape):
     x, y = _crop(_rendered_pair(), shape) if case == "rendered" else _noise_pair(shape, seed=sum(shape))
     if case == "rendered" and shape[0] == 3:                     # the case the loop sees: both clamps are active

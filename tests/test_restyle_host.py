@@ -118,6 +118,12 @@ def test_styles_entry_points_are_declared_and_exported(lib):
     assert "gsr_styles.hip" in _lib._SOURCES
 
 
+def test_every_library_source_exists():
+    assert "gsr_ssim.hip" in _lib._SOURCES
+    for name in _lib._SOURCES:
+        assert (ROOT / "styl3r_amd/csrc" / name).is_file(), name
+
+
 def test_styles_extra_bytes(lib):
     d0 = _lib.GsrDims(2, 5, 1000, 64, 64, 1, 0, 0, None)        # degree 0: per (style, scene, Gaussian)
     d2 = _lib.GsrDims(2, 5, 1000, 64, 64, 9, 2, 0, None)        # degree 2: per (style, view, Gaussian)
