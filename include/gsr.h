@@ -314,6 +314,42 @@ int gsr_ssim_structure_bwd(const float *target, const float *pred, const float *
                            int W, const float *window, float *grad_pred, void *stream);
 
 /*
+ * Point-map distillation (csrc/gsr_points.hip): the frozen DUSt3R / MASt3R teacher's head post-processing and the Regr3D loss
+ * (src/loss/loss_point.py:188-254) of the student's means against the teacher's point maps.  Device fp32, nothing syncs with the host,
+ * no float atomics, a launch sequence that depends on (B, N, mode) only; two runs give the same bits.
+ *
+ * pointmap_post: raw (P,4,H,W) head output -> pts3d (P,H,W,3) = xyz / max(|xyz|, 1e-8) * expm1(|xyz|), conf (P,H,W) = 1 + exp(raw[3]).
+ *
+ * regr3d_fwd: gt1, gt2 (B,N,3) and conf1, conf2 (B,N) contiguous; pr1, pr2 (B,N,3) with the (N,3) block of an image contiguous and
+ *   their own batch stride in floats (>= 3 N: the caller hands in means[:, 0] and means[:, 1] of a (b,v,h,w,1,3) tensor uncopied).
+ *     dis = |gt| per point; per (view, image) the 0.2 % and 99.8 % quantiles of dis exactly as torch.quantile's linear interpolation
+ *     (rank float32(q) * float32(N - 1), torch's lerp), found by radix selection, not by a sort; a NaN in a map makes both NaN;
+ *     valid = qlo <= dis <= qhi and conf >= 3;  with dist_clip > 0 instead: valid = dis <= dist_clip (no quantiles, no confidence gate);
+ *     norm = 1 ('avg_dis'): per image, jointly over both views, s = sum_valid |p| / (nnz1 + nnz2 + 1e-8), clipped below at 1e-8; the
+ *       prediction is divided by its s (with gradient), the teacher points by theirs; norm = 0: no normalisation;
+ *     loss = mean over view 1's valid points (all images together) of |pr1 - gt1| + the same for view 2; disable_view1 drops the first.
+ *   Deviation from the reference: a view without any valid point contributes 0 with a zero gradient (the reference returns NaN, the mean
+ *   of an empty tensor); status reports it.
+ *   status (2,B,2) int32: [view][image] = valid count, GSR_PT_* bits.  quantiles: NULL or (2,B,2) fp32 (zeros under dist_clip).
+ *   valid: NULL or (2,B,N) uint8.  scratch: regr3d_scratch_bytes(B, N) of device memory, uninitialised; the backward reads what the
+ *   forward left in it.
+ * regr3d_bwd: grad_pr1, grad_pr2 (B,N,3) contiguous = grad_loss[0] * d loss / d pr; every element is written (0 off the valid set and
+ *   where pr == gt); under norm = 1 the term through s is included.
+ * GSR_EINVAL before any launch: null pointers, B < 1, N < 2, a batch stride below 3 N, norm outside {0, 1}.
+ */
+#define GSR_PT_EMPTY_MAP 1    /* this (view, image) has no valid point */
+#define GSR_PT_NAN 2          /* |gt| of this map holds a NaN: NaN quantiles, nothing valid */
+#define GSR_PT_EMPTY_VIEW 4   /* the whole view has no valid point: its term is 0 */
+int gsr_pointmap_post(const float *raw, int64_t P, int H, int W, float *pts3d, float *conf, void *stream);
+size_t gsr_regr3d_scratch_bytes(int B, int64_t N);
+int gsr_regr3d_fwd(const float *gt1, const float *gt2, const float *conf1, const float *conf2, const float *pr1, const float *pr2,
+                   int64_t pr1_batch_stride, int64_t pr2_batch_stride, int B, int64_t N, int norm, int disable_view1, float dist_clip,
+                   void *scratch, float *loss, int32_t *status, float *quantiles, uint8_t *valid, void *stream);
+int gsr_regr3d_bwd(const float *gt1, const float *gt2, const float *pr1, const float *pr2, int64_t pr1_batch_stride,
+                   int64_t pr2_batch_stride, int B, int64_t N, int norm, int disable_view1, const float *grad_loss, const void *scratch,
+                   float *grad_pr1, float *grad_pr2, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

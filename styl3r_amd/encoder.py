@@ -660,12 +660,13 @@ def reg_dense_depth_exp(xyz: Tensor) -> Tensor:
 
 
 class PixelwiseTaskWithDPT(nn.Module):
-    def __init__(self, num_channels, net: CrocoTrunk, kind):
+    def __init__(self, num_channels, net: CrocoTrunk, kind, has_conf: bool = False):
         super().__init__()
         l2 = net.dec_depth
         assert l2 > 9
         ed, dd = net.enc_embed_dim, net.dec_embed_dim
         self.kind = kind
+        self.has_conf = has_conf       # the distillation teacher's heads: a fourth channel, conf mode ('exp', 1, inf)
         self.dpt = DPTAdapter(num_channels, [ed, dd, dd, dd], [0, l2 * 2 // 4, l2 * 3 // 4, l2], "pts3d" if kind == "pts3d_raw" else kind)
 
     def forward(self, tokens, image_size, imgs=None, raw: bool = False, layers=None):
@@ -673,6 +674,9 @@ class PixelwiseTaskWithDPT(nn.Module):
         (vit_adapter_fwd) applies reg_dense_depth itself.  layers: DPTAdapter.forward"""
         out = self.dpt(tokens, image_size, imgs, layers=layers)
         if self.kind == "pts3d" and not raw:
+            if self.has_conf:
+                from .points import pointmap_post
+                return pointmap_post(out)                  # {"pts3d", "conf"}: one pass on the device (gsr_pointmap_post)
             return {"pts3d": reg_dense_depth_exp(out.permute(0, 2, 3, 1))}
         return out
 
@@ -726,8 +730,10 @@ class _LinearGsHead(nn.Sequential):
 
 
 def head_factory(head_type, output_mode, net, has_conf=False, out_nchan=3):
-    """heads/__init__.py:13-27, all five branches."""
-    assert not has_conf
+    """heads/__init__.py:13-27, all five branches.  has_conf: the ('dpt', 'pts3d') head of the distillation teacher only."""
+    if has_conf:
+        assert head_type == "dpt" and output_mode == "pts3d", "a confidence channel exists for the ('dpt', 'pts3d') head only"
+        return PixelwiseTaskWithDPT(4, net, "pts3d", has_conf=True)
     if head_type == "linear" and output_mode == "pts3d":
         return LinearPts3d(net, has_conf)
     if head_type == "dpt" and output_mode == "gs_params":
@@ -1186,7 +1192,10 @@ class EncoderNoPoSplatTokenStyle(EncoderNoPoSplatMultiTokenStyle):
 
     restyle = encode_scene
 
-    def forward(self, context: dict, style: dict, global_step: int = 0, visualization_dump: Optional[dict] = None) -> Gaussians:
+    def forward(self, context: dict, style: dict, global_step: int = 0, visualization_dump: Optional[dict] = None,
+                distill_only: bool = False) -> Optional[Gaussians]:
+        """distill_only (`:164-183`, the point-map distillation stage): backbone -> StructureBuilder -> `downstream_head1` for both views;
+        fills visualization_dump["means"] (b,2,h,w,1,3) and returns None -- the stylizer and the Gaussian heads do not run."""
         b, v, _, h, w = context["image"].shape
         assert v == 2, "noposplat_token_style is the 2-view encoder"
         bb = self.backbone
@@ -1195,6 +1204,13 @@ class EncoderNoPoSplatTokenStyle(EncoderNoPoSplatMultiTokenStyle):
         feat, pos = bb._encode_image(images, token)
         feat, pos = feat.view(b, v, feat.shape[1], -1), pos.view(b, v, pos.shape[1], 2)
         st1, st2 = self.structure_builder(feat[:, 0], pos[:, 0], feat[:, 1], pos[:, 1])
+        if distill_only:
+            with torch.autocast("cuda", enabled=False):
+                both = [torch.cat((a, c), dim=0).float() for a, c in zip(st1, st2)]       # the shared head sees both views as one batch
+                pts = landscape_mean_head(self.downstream_head1, both, h, w)              # (2 b, h, w, 3), view-major
+            if visualization_dump is not None:
+                visualization_dump["means"] = torch.stack((pts[:b], pts[b:]), dim=1).reshape(b, v, h, w, 1, 3)
+            return None
         sty = self.token_stylizer(style, feat, pos)
         x_op = self.cfg.opacity_mapping
         exponent = 2 ** (x_op.initial + min(global_step / x_op.warm_up, 1) * (x_op.final - x_op.initial))

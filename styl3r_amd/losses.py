@@ -453,3 +453,99 @@ class LossSsimStructure(nn.Module):
         image = batch["target"]["image"]
         b, v = image.shape[:2]
         return self.weight * (1 - ssim_structure(image.reshape(b * v, *image.shape[2:]), prediction.color.reshape(b * v, *image.shape[2:])))
+
+
+# ---------------------------------------------------------------------------
+# Point-map distillation loss (src/loss/loss_point.py:188-254 `Regr3D`, src/geometry/ptc_geometry.py:270-328 `normalize_pointcloud`):
+# the student's means against the frozen teacher's point maps.
+# One deliberate deviation from the reference, on every path: a view whose valid set is empty contributes 0 with a zero gradient (the
+# reference returns NaN, the mean of an empty tensor).
+# ---------------------------------------------------------------------------
+REGR3D_QUANTILES = (0.002, 0.998)
+REGR3D_CONF_MIN = 3
+
+
+def _norm_factor(pts1: Tensor, pts2: Tensor, norm_mode: str, valid1: Tensor, valid2: Tensor):
+    """the per-image scale of `normalize_pointcloud`, jointly over both views, and the (possibly warped) points"""
+    how, dis_mode = norm_mode.split("_")
+    b = pts1.shape[0]
+    if how == "avg":
+        zero = torch.zeros_like(pts1[..., :1])
+        both = torch.cat((torch.where(valid1.unsqueeze(-1), pts1, zero).reshape(b, -1, 3), torch.where(valid2.unsqueeze(-1), pts2, zero).reshape(b, -1, 3)), dim=1)
+        nnz = valid1.reshape(b, -1).sum(1) + valid2.reshape(b, -1).sum(1)
+        dis = both.norm(dim=-1)
+        if dis_mode == "log1p":
+            dis = torch.log1p(dis)
+        elif dis_mode == "warp-log1p":
+            log_dis = torch.log1p(dis)
+            warp = log_dis / dis.clip(min=1e-8)
+            n1 = pts1[0].numel() // 3
+            pts1 = pts1 * warp[:, :n1].reshape(pts1.shape[:-1]).unsqueeze(-1)
+            pts2 = pts2 * warp[:, n1:].reshape(pts2.shape[:-1]).unsqueeze(-1)
+            dis = log_dis
+        elif dis_mode != "dis":
+            raise ValueError(f"bad dis_mode {dis_mode!r}")
+        factor = dis.sum(dim=1) / (nnz.to(dis.dtype) + 1e-8)
+    else:
+        nan = torch.full_like(pts1[..., :1], float("nan"))
+        both = torch.cat((torch.where(valid1.unsqueeze(-1), pts1, nan).reshape(b, -1, 3), torch.where(valid2.unsqueeze(-1), pts2, nan).reshape(b, -1, 3)), dim=1)
+        dis = both.norm(dim=-1)
+        if how == "median":
+            factor = dis.nanmedian(dim=1).values.detach()
+        elif how == "sqrt":
+            factor = dis.sqrt().nanmean(dim=1) ** 2
+        else:
+            raise ValueError(f"bad norm_mode {norm_mode!r}")
+    return pts1, pts2, factor.clip(min=1e-8).reshape(b, *([1] * (pts1.dim() - 1)))
+
+
+def normalize_pointcloud(pts1: Tensor, pts2: Tensor, norm_mode: str, valid1: Tensor, valid2: Tensor):
+    pts1, pts2, f = _norm_factor(pts1, pts2, norm_mode, valid1, valid2)
+    return pts1 / f, pts2 / f
+
+
+def regr3d_valid_masks(gt_pts1: Tensor, gt_pts2: Tensor, conf1: Tensor, conf2: Tensor, dist_clip=None):
+    """the valid sets of Regr3D: |gt| inside its per-image [0.2 %, 99.8 %] quantiles and confidence >= 3, or |gt| <= dist_clip"""
+    dis1, dis2 = gt_pts1.norm(dim=-1), gt_pts2.norm(dim=-1)
+    if dist_clip is not None:
+        return dis1 <= dist_clip, dis2 <= dist_clip, None
+    b = dis1.shape[0]
+    q = torch.tensor(REGR3D_QUANTILES, device=dis1.device, dtype=dis1.dtype)
+    shape = (b,) + (1,) * (dis1.dim() - 1)
+    q1, q2 = torch.quantile(dis1.reshape(b, -1), q, dim=1), torch.quantile(dis2.reshape(b, -1), q, dim=1)
+    valid1 = (dis1 >= q1[0].view(shape)) & (dis1 <= q1[1].view(shape)) & (conf1 >= REGR3D_CONF_MIN)
+    valid2 = (dis2 >= q2[0].view(shape)) & (dis2 <= q2[1].view(shape)) & (conf2 >= REGR3D_CONF_MIN)
+    return valid1, valid2, torch.stack((q1.t(), q2.t()))           # quantiles (2, B, 2)
+
+
+def regr3d_expression(gt_pts1: Tensor, gt_pts2: Tensor, pr_pts1: Tensor, pr_pts2: Tensor, conf1: Tensor, conf2: Tensor,
+                      norm_mode="avg_dis", gt_scale: bool = False, dist_clip=None, disable_view1: bool = False) -> Tensor:
+    """`Regr3D.forward` as plain torch ops in the inputs' dtype: the CPU path and, in float64, the yardstick of the kernels"""
+    valid1, valid2, _ = regr3d_valid_masks(gt_pts1, gt_pts2, conf1, conf2, dist_clip)
+    if norm_mode:
+        pr_pts1, pr_pts2 = normalize_pointcloud(pr_pts1, pr_pts2, norm_mode, valid1, valid2)
+        if not gt_scale:
+            gt_pts1, gt_pts2 = normalize_pointcloud(gt_pts1, gt_pts2, norm_mode, valid1, valid2)
+    mean = lambda t: t.mean() if t.numel() else t.sum()           # (empty valid set: 0, see above)
+    loss2 = mean(torch.norm(pr_pts2 - gt_pts2, dim=-1)[valid2])
+    if disable_view1:
+        return loss2
+    return mean(torch.norm(pr_pts1 - gt_pts1, dim=-1)[valid1]) + loss2
+
+
+class Regr3D(nn.Module):
+    """`Regr3D(norm_mode, alpha, gt_scale)` with the reference's forward signature.  fp32 device tensors with norm_mode None / 'avg_dis' run
+    on the HIP kernels (points.regr3d_hip: exact radix selection instead of torch.quantile's sorts, one fused mask / normalise / distance
+    pass each way; raises if libgsr_hip.so is missing); everything else -- CPU tensors, other dtypes, gt_scale, the other norm modes, none
+    of which a training wrapper uses -- is `regr3d_expression`."""
+
+    def __init__(self, norm_mode="avg_dis", alpha: float = 0.2, gt_scale: bool = False):
+        super().__init__()
+        self.norm_mode, self.alpha, self.gt_scale = norm_mode, alpha, gt_scale
+
+    def forward(self, gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1=None, conf2=None, dist_clip=None, disable_view1=False, details=None) -> Tensor:
+        from . import points
+        if (self.norm_mode in (None, "avg_dis") and not (self.norm_mode and self.gt_scale) and (dist_clip is None or dist_clip > 0)
+                and points.regr3d_hip_ok(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2)):
+            return points.regr3d_hip(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2, bool(self.norm_mode), disable_view1, dist_clip, details)
+        return regr3d_expression(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2, self.norm_mode, self.gt_scale, dist_clip, disable_view1)

@@ -1,11 +1,12 @@
 """Train step over the hot path (encoder -> decoder -> losses -> backward -> DP all-reduce -> clip -> AdamW), the
 part of `ModelWrapperStyle.training_step` / `configure_optimizers` (src/model/model_wrapper_style.py:118-232,
-843-916) that the benchmarks and the multi-GPU path need.  Everything else of the LightningModule (logging,
-video, validation, distillation) is out of scope."""
+843-916) that the benchmarks and the multi-GPU path need, with the point-map distillation of both wrappers (`:157-171`, `:233-242`,
+model_wrapper.py:187-196).  Everything else of the LightningModule (logging, video, validation) is out of scope."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence, Tuple
 
+import inspect
 import os
 
 import torch
@@ -16,13 +17,15 @@ from .ddp import BucketedGradReducer, broadcast_module_state
 from .losses import mse_loss
 
 
-def select_trainable(encoder: nn.Module) -> Tuple[List[nn.Parameter], List[nn.Parameter], List[str]]:
+def select_trainable(encoder: nn.Module, distill_only: bool = False) -> Tuple[List[nn.Parameter], List[nn.Parameter], List[str]]:
     """Parameter selection of `configure_optimizers` (model_wrapper_style.py:845-883), same substring rules on the same
     parameter names.  Returns (new_params [lr], pretrained_params [lr * backbone_lr_multiplier], frozen names);
     frozen parameters get `requires_grad = False` so nothing is tracked for them (`:866-868`).
       stylized     : train `*stylizer.dec*` + `gaussian_appearance_head`; fine-tune the style encoder
                      (`stylizer.enc*`, `stylizer.mask_token`, `stylizer.patch_embed`); freeze the rest.
-      not stylized : new = stylizer decoder, both Gaussian heads, intrinsic_encoder; everything else pretrained."""
+      not stylized : new = stylizer decoder, both Gaussian heads, intrinsic_encoder; everything else pretrained.
+      not stylized, distill_only (`:877-883`): new = `structure_builder` | `downstream_head`, pretrained = `backbone`; a parameter in
+                     neither group is left out of the optimizer (and of the gradient reducer) but keeps `requires_grad`, as there."""
     new, pre, frozen = [], [], []
     stylized = bool(getattr(encoder, "stylized", False))
     for name, p in encoder.named_parameters():
@@ -36,6 +39,11 @@ def select_trainable(encoder: nn.Module) -> Tuple[List[nn.Parameter], List[nn.Pa
             else:
                 p.requires_grad = False
                 frozen.append(name)
+        elif distill_only:
+            if "structure_builder" in name or "downstream_head" in name:
+                new.append(p)
+            elif "backbone" in name:
+                pre.append(p)
         else:
             if ("stylizer.dec" in name or "gaussian_appearance_head" in name or "gaussian_param_head" in name
                     or "intrinsic_encoder" in name):
@@ -101,21 +109,44 @@ class TrainStep:
     (`:211-229`).  `batch["style"]["image"]` is in [0,1] and mapped to [-1,1] for a stylized encoder (`:151-155`).
     `extra_losses` (only with `losses=None`): modules of the same interface added on top of the default MSE, which stays inside
     the composite kernels -- the reference's `/loss: [mse, lpips]` is `extra_losses=[LossLpips()]`; their image gradient enters
-    the same composite backward."""
+    the same composite backward.
+    `distiller`: a frozen teacher (distiller.Dust3R) whose point maps of context views 0 and 1 supervise the encoder's means
+    (`visualization_dump["means"][:, 0]` / `[:, 1]`) through `distiller_loss` -- default `Regr3D(norm_mode=None)` for an encoder that takes a
+    style and `Regr3D()` otherwise, the two wrappers' choice.  `distill_only`: the encoder runs with that flag, nothing is rendered and the
+    distillation loss is the total (`:157-171`); otherwise `distill_weight` (0.1 in both wrappers) times the loss is added to the render
+    losses while global_step <= distill_max_steps (`:233-242`)."""
 
     def __init__(self, encoder: nn.Module, decoder: nn.Module, lr: float = 2e-4, dist=None, bucket_bytes: int = 64 << 20,
                  clip: Optional[float] = 0.5, losses: Optional[Sequence[nn.Module]] = None,
                  identity_loss: Optional[nn.Module] = None, backbone_lr_multiplier: float = 0.1,
                  warm_up_steps: Optional[int] = None, max_steps: int = 100_000, force_collective: bool = False,
-                 dp_mode: Optional[str] = None, extra_losses: Optional[Sequence[nn.Module]] = None):
+                 dp_mode: Optional[str] = None, extra_losses: Optional[Sequence[nn.Module]] = None, distiller: Optional[nn.Module] = None,
+                 distill_max_steps: int = 1_000_000, distill_only: bool = False, distiller_loss: Optional[nn.Module] = None,
+                 distill_weight: float = 0.1):
         self.encoder, self.decoder, self.clip = encoder, decoder, clip
+        self.distiller, self.distill_only, self.distill_max_steps, self.distill_weight = distiller, bool(distill_only), distill_max_steps, distill_weight
+        self.distiller_loss = distiller_loss
+        sig = inspect.signature(encoder.forward).parameters
+        # (the non-style encoders -- forward(context, global_step, ...) -- are called without the style argument)
+        self.takes_style = "style" in sig or any(p.kind is inspect.Parameter.VAR_POSITIONAL for p in sig.values())
+        if distiller is not None:
+            distiller.eval()
+            for p in distiller.parameters():                              # convert_to_buffer(distiller): frozen
+                p.requires_grad = False
+            if self.distiller_loss is None:
+                from .losses import Regr3D
+                self.distiller_loss = Regr3D(norm_mode=None) if self.takes_style else Regr3D()
+        if distill_only and distiller is None:
+            raise ValueError("distill_only: the distillation loss is the whole objective, pass distiller=")
+        if distill_only and "distill_only" not in sig:
+            raise ValueError(f"distill_only: {type(encoder).__name__}.forward has no such stage (the 2-view style encoder has)")
         self.losses, self.identity_loss = (list(losses) if losses is not None else None), identity_loss
         if extra_losses and losses is not None:
             raise ValueError("TrainStep: extra_losses are added to the default (fused) MSE; with `losses` list every loss there instead")
         self.extra_losses = list(extra_losses or [])
         # identical replicas before anything else looks at the parameters (DDP semantics: rank 0's state wins)
         self.synced_bytes = broadcast_module_state(encoder, dist, force_collective=force_collective)
-        new, pre, self.frozen_names = select_trainable(encoder)
+        new, pre, self.frozen_names = select_trainable(encoder, self.distill_only)
         # bucket order = reverse registration order of the trainable parameters (autograd readiness)
         trainable = {id(p) for p in list(new) + list(pre)}
         self.dp_mode = dp_mode or DP_MODE
@@ -128,22 +159,40 @@ class TrainStep:
         self._weights = [p for p in encoder.parameters() if id(p) in trainable and p.dim() == 2]
         self.global_step = 0
 
-    def _render(self, ctx, style, tgt, mse_target=None):
-        g = self.encoder(ctx, style, self.global_step)
+    def _encode(self, ctx, style, dump=None, **kw):
+        if dump is not None:
+            kw["visualization_dump"] = dump
+        return self.encoder(ctx, style, self.global_step, **kw) if self.takes_style else self.encoder(ctx, self.global_step, **kw)
+
+    def _distillation(self, ctx, dump) -> torch.Tensor:
+        """the teacher's forward (no grad; issued before the student's backward) and the point loss on the dumped means of views 0 and 1"""
+        gt1, gt2 = self.distiller(ctx, False)
+        means = dump["means"]
+        return self.distiller_loss(gt1["pts3d"], gt2["pts3d"], means[:, 0].squeeze(-2), means[:, 1].squeeze(-2), gt1["conf"], gt2["conf"],
+                                   disable_view1=False)
+
+    def _render(self, ctx, style, tgt, mse_target=None, dump=None):
+        g = self._encode(ctx, style, dump)
         h, w = tgt["image"].shape[-2:]
         kw = {} if mse_target is None else {"mse_target": mse_target}     # LossMse inside the composite kernels (DecoderOutput.loss_mse)
         return g, self.decoder.forward(g, tgt["extrinsics"], tgt["intrinsics"], tgt["near"], tgt["far"], (h, w), **kw)
 
     def __call__(self, batch: dict) -> torch.Tensor:
-        ctx, tgt = batch["context"], batch["target"]
+        ctx, tgt = batch["context"], batch.get("target")                  # (distill_only renders nothing: no target needed)
         if getattr(self.encoder, "stylized", False) and "style" in batch:
             style = {"image": (batch["style"]["image"] - 0.5) / 0.5}     # (0,1) -> (-1,1), `:151-155`
         else:
             style = {"image": ctx["image"][:, 0]}                         # stylized=False: style := context view 0 (`:149-150`)
         self.reducer.wait_params()                                        # "rs_ag": the previous step's parameter all-gather must have landed
         self.reducer.prepare()
+        if self.distill_only:
+            dump = {}
+            self._encode(ctx, style, dump, distill_only=True)
+            return self._finish(self._distillation(ctx, dump))
+        distill = self.distiller is not None and self.global_step <= self.distill_max_steps
+        dump = {} if distill else None
         fuse = self.losses is None and tgt["image"].is_cuda and not tgt["image"].requires_grad
-        g, out = self._render(ctx, style, tgt, tgt["image"] if fuse else None)
+        g, out = self._render(ctx, style, tgt, tgt["image"] if fuse else None, dump)
         if self.losses is None:
             total = out.loss_mse if fuse else mse_loss(out.color, tgt["image"])     # LossMse
             for fn in self.extra_losses:                                   # e.g. LPIPS: its image gradient joins the fused MSE's
@@ -153,6 +202,11 @@ class TrainStep:
         if self.identity_loss is not None:
             ig, iout = self._render(ctx, {"image": ctx["image"][:, 0]}, tgt)
             total = total + self.identity_loss(iout, batch, ig, self.global_step)
+        if distill:
+            total = total + self._distillation(ctx, dump) * self.distill_weight
+        return self._finish(total)
+
+    def _finish(self, total: torch.Tensor) -> torch.Tensor:
         total.backward()
         self.reducer.finish()
         if self.clip is not None:                                         # Trainer(gradient_clip_val=0.5), main_style.py:110
