@@ -131,6 +131,11 @@ typedef struct GsrLayout {
     size_t ckpt;         /* checkpoint slots of 256 pixels, 5 KiB each: float4 (T, r, g, b prefix)[4 quadrants][64 lanes], then float depth
                             prefix[4][64].  Tile t's boundary m L (m = 1, 2, ...) is slot tile_offset[t] / L + m - 1: at most cap / L slots */
     size_t unit_order;   /* uint32[2][units] (view*T + tile, depth segment) work units of the composite backward, longest first */
+    size_t geo;          /* float4[V*G]     bit-exact copy of each record's first 16 bytes (x, y, depth, radius+flags): the scatter and the
+                            preprocess backward stream these instead of striding through the 48-byte records */
+    size_t opac;         /* float[B*G]      the opacities the forward read, kept for the preprocess backward */
+    size_t scan;         /* uint32[1024 + 8 * ceil(V*T / 256)]  what the launches of the tile scan hand each other: class counts, class cursors,
+                            per-workgroup partial sums */
     size_t total;        /* total bytes */
 } GsrLayout;
 

@@ -275,6 +275,10 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(GsrDims d, const GsrView
     for (int k = 0; k < 3 * NC; ++k) dsh_acc[k] = 0.f;
 
     float dmean[3] = {0.f, 0.f, 0.f}, dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dop = 0.f;
+    // Of the 48-B splat record this kernel needs rad_flags (geo), the opacity (the forward's per-Gaussian copy) and the conic, which it forms from
+    // its own geom_eval with K1's expressions under the same fp contract(off): bit-identical to the stored one.  (Round 15; before, it streamed
+    // two float4 of every record at the 48-byte stride, i.e. every cache line of the array.)
+    const float op = ws.opac[sg];
 
     for (int j = 0; j < d.Vt; ++j) {
         const int v = b * d.Vt + j;
@@ -283,12 +287,11 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(GsrDims d, const GsrView
         const size_t vg = (size_t)v * d.G + (valid ? g : 0);
         float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         float g2x = 0.f, g2y = 0.f;
-        // the record and the summed gradient record of this (view, Gaussian): five independent 16-byte loads issued together, in front of
-        // the visibility test.  The kernel is LATENCY-bound (round 5: with contraction on and v_rcp_f32 for its reciprocals, -13 % instructions,
+        // the geometry record and the summed gradient record of this (view, Gaussian): four independent 16-byte loads issued together, in
+        // front of the visibility test.  The kernel is LATENCY-bound (round 5: with contraction on and v_rcp_f32 for its reciprocals, -13 % instructions,
         // it did not move); before, the gradient record was fetched inside `if (vis)`, one memory round trip behind the record: 0.067 -> 0.052 ms
         // at the headline, 0.258 -> 0.215 at 262 144 Gaussians.  (Fetching one view AHEAD on top of this: no further gain, +12 registers.)
-        const float4 q0 = reinterpret_cast<const float4 *>(ws.records + vg)[0];
-        const float4 q1 = reinterpret_cast<const float4 *>(ws.records + vg)[1];      // A, B, C, opacity
+        const float4 q0 = ws.geo[vg];
         float gr[GR_STRIDE];
         {
             const float4 *g4 = reinterpret_cast<const float4 *>(ws.grad_rec + vg * GR_STRIDE);
@@ -350,7 +353,9 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(GsrDims d, const GsrView
             const float k2 = 1.0f / (denom * denom + 0.0000001f);
             // K6 leaves the moments of t = dL/dalpha G over the splat's pixels: sum t dx, sum t dy, sum t dx^2, sum t dx dy, sum t dy^2;
             // dL_dG G = opacity t, and the conic / mean terms carry -1/2 of it: one factor per (view, Gaussian), applied here
-            const float kop = -0.5f * q1.w;
+            const float det_inv = 1.0f / denom;              // K1's det_inv: denom is its `det`, non-zero for every visible splat
+            const float cA = c * det_inv, cB = -bb * det_inv, cC = a * det_inv;
+            const float kop = -0.5f * op;
             const float gA = kop * gr[GR_CA], gB = kop * gr[GR_CB], gC = kop * gr[GR_CC];
             const float ga = k2 * (-c * c * gA + 2.0f * bb * c * gB + (denom - a * c) * gC);
             const float gc = k2 * (-a * a * gC + 2.0f * a * bb * gB + (denom - a * c) * gA);
@@ -406,8 +411,8 @@ __global__ void __launch_bounds__(256) k_preprocess_bwd(GsrDims d, const GsrView
             const float mul1 = hx * mw * mw, mul2 = hy * mw * mw;
             {   // K6 accumulated hx = sum(-dL_dG/2 G dx), hy likewise: mean2D gradient = (A hx + B hy) W, (C hy + B hx) H
                 const float sx = kop * gr[GR_MX], sy = kop * gr[GR_MY];
-                g2x = (q1.x * sx + q1.y * sy) * (float)d.W;
-                g2y = (q1.z * sy + q1.y * sx) * (float)d.H;
+                g2x = (cA * sx + cB * sy) * (float)d.W;
+                g2y = (cC * sy + cB * sx) * (float)d.H;
             }
 #pragma unroll
             for (int k = 0; k < 3; ++k)

@@ -53,6 +53,9 @@ struct Ptrs {             // carved workspace
     float4 *final_C;        // (r, g, b, depth) the composite forward accumulated, background not added (tiles of > 1 segment)
     float *ckpt;            // depth-segment checkpoints, CKPT_SLOT_FLOATS per (tile, boundary)
     uint2 *unit_order;      // (view*T + tile, segment) work units of the composite backward, longest first
+    float4 *geo;            // (x, y, depth, rad_flags): the records' first float4, densely packed for the kernels that stream it (K3, K7)
+    float *opac;            // [B*G] the opacities as K1 read them, for K7
+    uint32_t *scan;         // tile scan: 512 class counts, 512 class cursors, one 8-word partial record per 256 counters (gsr_forward.hip K2)
 };
 
 }  // namespace gsr

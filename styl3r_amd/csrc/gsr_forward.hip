@@ -2,11 +2,13 @@
 //
 //   K1 preprocess      per Gaussian, loops over the scene's views: cull, cov3D->2D, conic,
 //                      radius, tile rect, SH colour; writes one 48-B SplatRec per (view,
-//                      Gaussian) and counts the per-tile list lengths through a per-workgroup
+//                      Gaussian), a dense copy of its first 16 bytes (`geo`, what K3 and K7
+//                      stream) and counts the per-tile list lengths through a per-workgroup
 //                      LDS histogram (one global atomic per non-empty (workgroup, tile)). (upstream R1)
-//   K2 scan_tiles      exclusive scan of the V*T tile counters (one workgroup), the status
-//                      words (pair count, overflow, longest list), the longest-list-first
-//                      launch order of K4 - K6; re-arms persistent counters.             (R2)
+//   K2 scan_tiles      exclusive scan of the V*T tile counters, the status words (pair count,
+//                      overflow, longest list), the longest-list-first launch order of
+//                      K4 - K6; re-arms persistent counters.  Three launches of one
+//                      workgroup per 256 counters.                                  (R2, R15)
 //   K3 scatter         every (view, Gaussian, tile) pair -> its tile bucket as
 //                      (depth_bits<<32 | id), slots handed out from LDS.                 (R3)
 //   K4 tile_sort       per-tile depth sort in LDS: one MSD radix pass over the 8 most
@@ -57,6 +59,7 @@ __global__ void __launch_bounds__(256) k_preprocess(GsrDims d, const GsrView *__
     float S0[6];
     load_cov(cov6, sg, (d.flags & GSR_FLAG_COV9) != 0, S0);
     const float op = opac[sg];
+    if (live) ws.opac[sg] = op;                // the backward's copy: gsr_backward is not handed the opacities
     const int gx = tiles_x(d.W), gy = tiles_y(d.H), T = gx * gy;
     if (lds_tiles) {
         for (int t = threadIdx.x; t < T; t += 256) s_tiles[t] = 0u;
@@ -153,6 +156,7 @@ __global__ void __launch_bounds__(256) k_preprocess(GsrDims d, const GsrView *__
             float4 *dst = reinterpret_cast<float4 *>(ws.records + vg);
             const float4 *src = reinterpret_cast<const float4 *>(&rec);
             dst[0] = src[0]; dst[1] = src[1]; dst[2] = src[2];
+            ws.geo[vg] = src[0];      // the dense copy K3 and K7 stream (16 B per entry instead of a 48-B stride)
             radii[vg] = rad * (ok ? 1 : 0);
         }
     }
@@ -160,204 +164,207 @@ __global__ void __launch_bounds__(256) k_preprocess(GsrDims d, const GsrView *__
 #pragma clang fp contract(fast)
 
 // ------------------------------------------------------------------ K2
-// One workgroup of 1024 threads scans n = V*T counters (n is at most a few 10^4).
-// Fast path (n <= 16 384 counters, e.g. 40 views x 256 tiles): the counters go through LDS once (coalesced loads), every
-// thread then owns PER consecutive counters in registers: serial scan of its own, one wave scan + one cross-wave fix-up
-// of the thread totals -- 6 barriers instead of 3 per 1 024 counters.
-constexpr int SCAN_PER_MAX = 16;
+// The scan of the n = V*T tile counters, the status words and the launch orders of K4 - K6, as three short launches of one 256-thread
+// workgroup per SCAN_CHUNK counters (round 15; before: ONE workgroup of 1 024 threads, 34 us at the headline with 255 CUs idle).  Workgroups
+// hand data to each other only across the kernel boundaries -- nothing waits on another workgroup, and no launch reads bytes another workgroup
+// of the same launch wrote (the returning atomics of the placement are the one exchange inside a launch: they only reserve disjoint ranges):
+//   k_scan_partials   every workgroup: (sum, max, full units, non-empty tiles) of its chunk -> ws.scan partial record; workgroup 0 zeroes the
+//                     loss tickets and the class bins / cursors of the two launches below.
+//   k_scan_offsets    every workgroup reduces all partial records itself (40 at the headline): its base, R, the longest list m, the class
+//                     shifts; finalises tile_offset (exact exclusive scan, saturated at 2^32 - 1) and zeroes the cursors; workgroup 0 stores the
+//                     status words; LDS histograms of the 256 tile classes and 256 unit classes, one global add per non-empty (workgroup, class).
+//   k_scan_place      every workgroup scans the 512 bins itself, reserves one range per non-empty (workgroup, class) with a returning global
+//                     add and hands out positions from LDS (the pattern of k_scatter_lds): tile_order, unit_order.  Last reader of the
+//                     counters: re-arms persistent ones.
+// Launch order of the composite kernels: longest lists first (counting sort into 256 length classes), so the workgroups that take longest
+// start first and the tail of K5 / K6 is made of short tiles (LPT scheduling).  K6's work units: a tile of c entries is ceil(c / L) units,
+// ceil(c / L) - 1 "full" ones of length L and the last one of the rest.  The full units come first, in tile order at the positions an
+// exclusive scan of their counts gives (round 7: one counter for all of them serialised ~2 * 10^4 atomics on one address, 16 -> 82 us); the
+// last units follow, longest first by the same counting sort as the tiles.  (After an overflow there is no unit table: the unit count stays 0.)
+constexpr int SCAN_CHUNK = 256;          // counters per workgroup, one per thread
+constexpr int SCAN_PART_WORDS = 8;       // partial record: sum lo, sum hi, max, full units, non-empty tiles, 3 unused
+constexpr int SCAN_BINS = 512;           // 256 tile classes, then 256 unit classes
+// ws.scan: [SCAN_BINS] class counts, [SCAN_BINS] class cursors, then the partial records
+__host__ __device__ inline size_t scan_words(size_t n) { return 2 * SCAN_BINS + (n + SCAN_CHUNK - 1) / SCAN_CHUNK * SCAN_PART_WORDS; }
 
-// `rearm`: the counters are the caller's persistent ones (GsrFused.tile_count): leave them zero for the next forward.
-// `nticket`: fused-MSE arrival counters of this workspace to zero (0 = none).
-// `seg`, `umax`: segment length and unit capacity of K6's work-unit table (seg_len, unit_capacity).
-__global__ void __launch_bounds__(1024) k_scan_tiles(int n, long long capacity, Ptrs ws, int32_t *__restrict__ status, int rearm, int nticket,
-                                                     uint32_t seg, uint32_t umax)
+__device__ inline uint32_t units_full(uint32_t cnt, uint32_t seg) { return cnt ? (cnt - 1u) / seg : 0u; }
+
+// exclusive scan of one value per thread over the 256 threads of the workgroup; `total` = the sum.  s4: 4 words of LDS, free again on return.
+template <typename T>
+__device__ inline T block_excl_scan_256(T v, T *s4, T &total)
 {
-    __shared__ unsigned long long s_wave[16];
-    __shared__ unsigned long long s_carry;
-    __shared__ uint32_t s_max[16];
-    __shared__ uint32_t s_bin[256], s_shift;
-    __shared__ uint32_t s_ubin[256], s_ushift, s_ovf, s_units, s_full, s_fcur, s_fw[16];
-    __shared__ uint32_t s_cnt[1024 * SCAN_PER_MAX];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    uint32_t mx = 0;
-    const int per = (n + 1023) / 1024;
-    const bool fast = per <= SCAN_PER_MAX;
-    uint32_t c[SCAN_PER_MAX];
-    if (fast) {
-        for (int i = tid; i < per * 1024; i += 1024) s_cnt[i] = (i < n) ? ws.tile_count[i] : 0u;
-        if (rearm) for (int i = tid; i < n; i += 1024) ws.tile_count[i] = 0u;       // (read above by the same thread)
-        for (int i = tid; i < nticket; i += 1024) ws.loss_ticket[i] = 0u;
-        __syncthreads();
-        unsigned long long tot = 0;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    T x = v;
 #pragma unroll
-        for (int e = 0; e < SCAN_PER_MAX; ++e) {
-            c[e] = (e < per) ? s_cnt[tid * per + e] : 0u;
-            mx = max(mx, c[e]);
-            tot += c[e];
-        }
-        unsigned long long x = tot;                       // inclusive scan of the thread totals inside the wave
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            unsigned long long y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) s_wave[wid] = x;
-        __syncthreads();
-        unsigned long long off = x - tot;
-        for (int w = 0; w < wid; ++w) off += s_wave[w];
-        if (tid == 1023) s_carry = off + tot;
-#pragma unroll
-        for (int e = 0; e < SCAN_PER_MAX; ++e) {
-            const int i = tid * per + e;
-            if (e < per && i < n) {
-                ws.tile_offset[i] = (uint32_t)min(off, (unsigned long long)0xffffffffu);
-                ws.tile_cursor[i] = 0u;
-            }
-            off += c[e];
-        }
-    } else {
-        if (tid == 0) s_carry = 0;
-        for (int i = tid; i < nticket; i += 1024) ws.loss_ticket[i] = 0u;
-        __syncthreads();
-        for (int base = 0; base < n; base += 1024) {
-            int i = base + tid;
-            uint32_t cc = (i < n) ? ws.tile_count[i] : 0u;
-            mx = max(mx, cc);
-            unsigned long long x = cc;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                unsigned long long y = __shfl_up(x, o, 64);
-                if (lane >= o) x += y;
-            }
-            if (lane == 63) s_wave[wid] = x;
-            __syncthreads();
-            unsigned long long wave_off = 0;
-            for (int w = 0; w < wid; ++w) wave_off += s_wave[w];
-            unsigned long long carry = s_carry;
-            unsigned long long excl = carry + wave_off + x - cc;
-            if (i < n) {
-                ws.tile_offset[i] = (uint32_t)min(excl, (unsigned long long)0xffffffffu);
-                ws.tile_cursor[i] = 0u;
-            }
-            __syncthreads();
-            if (tid == 1023) s_carry = carry + wave_off + x;
-            __syncthreads();
-        }
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
     }
-    // block max of the tile lengths
+    if (lane == 63) s4[wid] = x;
+    __syncthreads();
+    T off = x - v;
+    for (int w = 0; w < wid; ++w) off += s4[w];
+    total = s4[0] + s4[1] + s4[2] + s4[3];
+    __syncthreads();
+    return off;
+}
+
+// what every workgroup of the second and third launch derives from ALL partial records (written by the launch before)
+struct ScanTotals {
+    unsigned long long R, base;      // all pairs ; pairs in front of this workgroup's chunk
+    uint32_t m, full, full_base, nonempty;   // longest list ; full units: all, in front of this chunk ; non-empty tiles
+    uint32_t shift, ushift;          // class = 255 - min(len >> shift, 255)
+    bool units;                      // no overflow: the unit table is built
+};
+__device__ inline ScanTotals scan_totals(const uint32_t *__restrict__ part, int nwg, long long capacity, uint32_t seg, unsigned long long *s_red /* [4 * 6] */)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    unsigned long long R = 0, base = 0, full = 0, fbase = 0, ne = 0, m = 0;
+    for (int p = tid; p < nwg; p += SCAN_CHUNK) {
+        const uint32_t *r = part + (size_t)p * SCAN_PART_WORDS;
+        const unsigned long long sum = ((unsigned long long)r[1] << 32) | r[0];
+        R += sum; full += r[3]; ne += r[4];
+        m = max(m, (unsigned long long)r[2]);
+        if (p < (int)blockIdx.x) { base += sum; fbase += r[3]; }
+    }
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
-    if (lane == 0) s_max[wid] = mx;
-    if (tid < 256) { s_bin[tid] = 0u; s_ubin[tid] = 0u; }
+    for (int o = 32; o > 0; o >>= 1) {
+        R += __shfl_xor(R, o, 64); base += __shfl_xor(base, o, 64); full += __shfl_xor(full, o, 64);
+        fbase += __shfl_xor(fbase, o, 64); ne += __shfl_xor(ne, o, 64); m = max(m, (unsigned long long)__shfl_xor(m, o, 64));
+    }
+    if (lane == 0) {
+        unsigned long long *d = s_red + wid * 6;
+        d[0] = R; d[1] = base; d[2] = full; d[3] = fbase; d[4] = ne; d[5] = m;
+    }
+    __syncthreads();
+    ScanTotals t;
+    t.R = s_red[0] + s_red[6] + s_red[12] + s_red[18];
+    t.base = s_red[1] + s_red[7] + s_red[13] + s_red[19];
+    t.full = (uint32_t)(s_red[2] + s_red[8] + s_red[14] + s_red[20]);
+    t.full_base = (uint32_t)(s_red[3] + s_red[9] + s_red[15] + s_red[21]);
+    t.nonempty = (uint32_t)(s_red[4] + s_red[10] + s_red[16] + s_red[22]);
+    t.m = (uint32_t)max(max(s_red[5], s_red[11]), max(s_red[17], s_red[23]));
+    __syncthreads();
+    t.units = !(t.R > (unsigned long long)capacity || t.R > 0xffffffffull);
+    uint32_t sh = 0;                           // 256 length classes covering [0, m]
+    while ((t.m >> sh) > 255u) ++sh;
+    t.shift = sh;
+    const uint32_t um = min(t.m, seg);         // units are at most min(m, L) long
+    sh = 0;
+    while ((um >> sh) > 255u) ++sh;
+    t.ushift = sh;
+    return t;
+}
+
+// `nticket`: fused-MSE arrival counters of this workspace to zero (0 = none).  `seg`: segment length of K6's work units (seg_len).
+__global__ void __launch_bounds__(SCAN_CHUNK) k_scan_partials(int n, Ptrs ws, int nticket, uint32_t seg)
+{
+    __shared__ unsigned long long s_red[4 * 4];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int i = blockIdx.x * SCAN_CHUNK + tid;
+    if (blockIdx.x == 0) {
+        for (int k = tid; k < nticket; k += SCAN_CHUNK) ws.loss_ticket[k] = 0u;
+        for (int k = tid; k < 2 * SCAN_BINS; k += SCAN_CHUNK) ws.scan[k] = 0u;
+    }
+    const uint32_t c = (i < n) ? ws.tile_count[i] : 0u;
+    unsigned long long sum = c, mx = c, full = units_full(c, seg), ne = c ? 1u : 0u;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        sum += __shfl_xor(sum, o, 64); full += __shfl_xor(full, o, 64); ne += __shfl_xor(ne, o, 64);
+        mx = max(mx, (unsigned long long)__shfl_xor(mx, o, 64));
+    }
+    if (lane == 0) { s_red[wid * 4] = sum; s_red[wid * 4 + 1] = mx; s_red[wid * 4 + 2] = full; s_red[wid * 4 + 3] = ne; }
     __syncthreads();
     if (tid == 0) {
-        uint32_t m = 0;
-        for (int w = 0; w < 16; ++w) m = max(m, s_max[w]);
-        unsigned long long R = s_carry;
-        ws.tile_offset[n] = (uint32_t)min(R, (unsigned long long)0xffffffffu);
-        int ovf = (R > (unsigned long long)capacity || R > 0xffffffffull) ? 1 : 0;
-        int32_t st[GSR_STATUS_WORDS] = {(int32_t)(R & 0xffffffffull), ovf, (int32_t)m, (int32_t)(R >> 32), 0, 0, 0, 0};
-        for (int k = 0; k < GSR_STATUS_WORDS; ++k) { status[k] = st[k]; ws.status[k] = st[k]; }   // (GSR_ST_UNITS: below, same thread)
-        uint32_t sh = 0;                       // 256 length classes covering [0, m]
-        while ((m >> sh) > 255u) ++sh;
-        s_shift = sh;
-        const uint32_t um = min(m, seg);       // units are at most min(m, L) long
-        sh = 0;
-        while ((um >> sh) > 255u) ++sh;
-        s_ushift = sh;
-        s_ovf = (uint32_t)ovf;
-        s_full = 0u; s_fcur = 0u;
+        sum = s_red[0] + s_red[4] + s_red[8] + s_red[12];
+        uint32_t *r = ws.scan + 2 * SCAN_BINS + (size_t)blockIdx.x * SCAN_PART_WORDS;
+        r[0] = (uint32_t)sum; r[1] = (uint32_t)(sum >> 32);
+        r[2] = (uint32_t)max(max(s_red[1], s_red[5]), max(s_red[9], s_red[13]));
+        r[3] = (uint32_t)(s_red[2] + s_red[6] + s_red[10] + s_red[14]);     // (wraps only beyond 2^32 pairs: an overflow, no unit table)
+        r[4] = (uint32_t)(s_red[3] + s_red[7] + s_red[11] + s_red[15]);
+    }
+}
+
+__global__ void __launch_bounds__(SCAN_CHUNK) k_scan_offsets(int n, long long capacity, Ptrs ws, int32_t *__restrict__ status, uint32_t seg)
+{
+    __shared__ unsigned long long s_red[4 * 6];
+    __shared__ uint32_t s_bin[SCAN_BINS];
+    const int tid = threadIdx.x;
+    const int i = blockIdx.x * SCAN_CHUNK + tid;
+    const uint32_t c = (i < n) ? ws.tile_count[i] : 0u;             // (issued in front of the reduction's barriers)
+    s_bin[tid] = 0u; s_bin[SCAN_CHUNK + tid] = 0u;
+    const ScanTotals t = scan_totals(ws.scan + 2 * SCAN_BINS, gridDim.x, capacity, seg, s_red);
+    unsigned long long total;
+    const unsigned long long off = t.base + block_excl_scan_256<unsigned long long>(c, s_red, total);
+    if (i < n) {
+        ws.tile_offset[i] = (uint32_t)min(off, (unsigned long long)0xffffffffu);
+        ws.tile_cursor[i] = 0u;
+        atomicAdd(&s_bin[255u - min(c >> t.shift, 255u)], 1u);
+        if (t.units && c) atomicAdd(&s_bin[256u + 255u - min((c - units_full(c, seg) * seg) >> t.ushift, 255u)], 1u);
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        ws.tile_offset[n] = (uint32_t)min(t.R, (unsigned long long)0xffffffffu);
+        const int32_t st[GSR_STATUS_WORDS] = {(int32_t)(t.R & 0xffffffffull), t.units ? 0 : 1, (int32_t)t.m, (int32_t)(t.R >> 32),
+                                              t.units ? (int32_t)(t.full + t.nonempty) : 0, 0, 0, 0};
+        for (int k = 0; k < GSR_STATUS_WORDS; ++k) { status[k] = st[k]; ws.status[k] = st[k]; }
     }
     __syncthreads();
-    // Launch order of the composite kernels: longest lists first (counting sort into 256 length classes), so the
-    // workgroups that take longest start first and the tail of K5 / K6 is made of short tiles (LPT scheduling).
-    // K6's work units: a tile of n entries is ceil(n / L) units, ceil(n / L) - 1 "full" ones of length L and the last one of the rest.
-    // The full units come first, in tile order at the positions an exclusive scan of their counts gives (round 7: one LDS counter for
-    // all of them serialised ~2 * 10^4 atomics on one address, 16 -> 82 us for this kernel at the headline); the last units follow,
-    // longest first by the same counting sort as the tiles.  (After an overflow there is no unit table: the unit count stays 0.)
-    const uint32_t sh = s_shift, ush = s_ushift;
-    const bool units = s_ovf == 0u;
-    auto ucls = [&](uint32_t len) { return 255u - min(len >> ush, 255u); };
-    auto nfull = [&](uint32_t cnt) { return cnt ? (cnt - 1u) / seg : 0u; };
-    uint32_t fbase = 0;                        // fast path: position of this thread's first full unit
-    if (units && fast) {                       // (uniform)
-        uint32_t fs = 0;
 #pragma unroll
-        for (int e = 0; e < SCAN_PER_MAX; ++e) if (e < per) fs += nfull(c[e]);
-        uint32_t x = fs;
+    for (int k = 0; k < SCAN_BINS; k += SCAN_CHUNK) {
+        const uint32_t b = s_bin[k + tid];
+        if (b) atomicAdd(ws.scan + k + tid, b);
+    }
+}
+
+// `rearm`: the counters are the caller's persistent ones (GsrFused.tile_count): leave them zero for the next forward.
+// `umax`: capacity of the unit table (unit_capacity).
+__global__ void __launch_bounds__(SCAN_CHUNK) k_scan_place(int n, long long capacity, Ptrs ws, int rearm, uint32_t seg, uint32_t umax)
+{
+    __shared__ unsigned long long s_red[4 * 6];
+    __shared__ uint32_t s_base[SCAN_BINS], s_cnt[SCAN_BINS], s4[4];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int i = blockIdx.x * SCAN_CHUNK + tid;
+    const uint32_t c = (i < n) ? ws.tile_count[i] : 0u;
+    if (rearm && i < n) ws.tile_count[i] = 0u;                      // its last read
+    s_base[tid] = ws.scan[tid]; s_base[SCAN_CHUNK + tid] = ws.scan[SCAN_CHUNK + tid];
+    s_cnt[tid] = 0u; s_cnt[SCAN_CHUNK + tid] = 0u;
+    const ScanTotals t = scan_totals(ws.scan + 2 * SCAN_BINS, gridDim.x, capacity, seg, s_red);     // (its barriers order the LDS stores above)
+    const uint32_t nf = units_full(c, seg);
+    const uint32_t cls = 255u - min(c >> t.shift, 255u);
+    const uint32_t ucl = 256u + 255u - min((c - nf * seg) >> t.ushift, 255u);
+    const bool unit = t.units && c != 0u;
+    if (i < n) {
+        atomicAdd(&s_cnt[cls], 1u);
+        if (unit) atomicAdd(&s_cnt[ucl], 1u);
+    }
+    if (tid < 128) {                           // exclusive scans of the 256 tile bins (wave 0) and unit bins (wave 1), 4 bins per lane
+        uint32_t *bins = s_base + (tid < 64 ? 0 : 256);
+        const uint32_t b0 = bins[lane * 4], b1 = bins[lane * 4 + 1], b2 = bins[lane * 4 + 2], b3 = bins[lane * 4 + 3];
+        const uint32_t t4 = b0 + b1 + b2 + b3;
+        uint32_t x = t4;
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
             const uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
             if (lane >= o) x += y;
         }
-        if (lane == 63) s_fw[wid] = x;
-        __syncthreads();
-        fbase = x - fs;
-        for (int w = 0; w < wid; ++w) fbase += s_fw[w];
-        if (tid == 1023) s_full = fbase + fs;
-    }
-    auto ucount = [&](uint32_t cnt) {
-        if (!units || cnt == 0u) return;
-        if (!fast && cnt > seg) atomicAdd(&s_full, nfull(cnt));
-        atomicAdd(&s_ubin[ucls(cnt - nfull(cnt) * seg)], 1u);
-    };
-    auto uplace = [&](uint32_t i, uint32_t cnt) {
-        if (!units || cnt == 0u) return;
-        const uint32_t nf = nfull(cnt);
-        if (nf) {
-            const uint32_t p = fast ? fbase : atomicAdd(&s_fcur, nf);
-            fbase += nf;
-            for (uint32_t s = 0; s < nf; ++s)
-                if (p + s < umax) ws.unit_order[p + s] = make_uint2(i, s);
-        }
-        const uint32_t p = s_full + atomicAdd(&s_ubin[ucls(cnt - nf * seg)], 1u);
-        if (p < umax) ws.unit_order[p] = make_uint2(i, nf);
-    };
-    if (fast) {
-#pragma unroll
-        for (int e = 0; e < SCAN_PER_MAX; ++e)
-            if (e < per && tid * per + e < n) { atomicAdd(&s_bin[255u - min(c[e] >> sh, 255u)], 1u); ucount(c[e]); }
-    } else {
-        for (int i = tid; i < n; i += 1024) {
-            const uint32_t cnt = ws.tile_count[i];
-            atomicAdd(&s_bin[255u - min(cnt >> sh, 255u)], 1u);
-            ucount(cnt);
-        }
-    }
-    __syncthreads();
-    if (tid < 128) {                           // exclusive scans of the 256 tile bins (wave 0) and unit bins (wave 1), 4 bins per lane
-        uint32_t *bins = tid < 64 ? s_bin : s_ubin;
-        uint32_t b0 = bins[lane * 4], b1 = bins[lane * 4 + 1], b2 = bins[lane * 4 + 2], b3 = bins[lane * 4 + 3];
-        uint32_t t4 = b0 + b1 + b2 + b3, x = t4;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            uint32_t y = (uint32_t)__shfl_up((int)x, o, 64);
-            if (lane >= o) x += y;
-        }
-        uint32_t off = x - t4;
+        const uint32_t off = x - t4;
         bins[lane * 4] = off; bins[lane * 4 + 1] = off + b0; bins[lane * 4 + 2] = off + b0 + b1; bins[lane * 4 + 3] = off + b0 + b1 + b2;
-        if (tid == 127) s_units = x;
     }
     __syncthreads();
-    if (tid == 0) { status[GSR_ST_UNITS] = (int32_t)(s_full + s_units); ws.status[GSR_ST_UNITS] = (int32_t)(s_full + s_units); }
-    if (fast) {
 #pragma unroll
-        for (int e = 0; e < SCAN_PER_MAX; ++e) {
-            const int i = tid * per + e;
-            if (e < per && i < n) {
-                ws.tile_order[atomicAdd(&s_bin[255u - min(c[e] >> sh, 255u)], 1u)] = (uint32_t)i;
-                uplace((uint32_t)i, c[e]);
-            }
-        }
-    } else {
-        for (int i = tid; i < n; i += 1024) {
-            const uint32_t cnt = ws.tile_count[i];
-            const uint32_t pos = atomicAdd(&s_bin[255u - min(cnt >> sh, 255u)], 1u);
-            ws.tile_order[pos] = (uint32_t)i;
-            uplace((uint32_t)i, cnt);
-            if (rearm) ws.tile_count[i] = 0u;      // its last read
-        }
+    for (int k = 0; k < SCAN_BINS; k += SCAN_CHUNK) {          // one range per non-empty (workgroup, class)
+        const uint32_t b = s_cnt[k + tid];
+        if (b) { s_base[k + tid] += atomicAdd(ws.scan + SCAN_BINS + k + tid, b); s_cnt[k + tid] = 0u; }
     }
+    uint32_t ftotal;
+    const uint32_t fpos = t.full_base + block_excl_scan_256<uint32_t>(unit ? nf : 0u, s4, ftotal);   // (its barriers order the LDS updates above)
+    if (i >= n) return;
+    ws.tile_order[s_base[cls] + atomicAdd(&s_cnt[cls], 1u)] = (uint32_t)i;
+    if (!unit) return;
+    for (uint32_t s = 0; s < nf; ++s)
+        if (fpos + s < umax) ws.unit_order[fpos + s] = make_uint2((uint32_t)i, s);
+    const uint32_t p = t.full + s_base[ucl] + atomicAdd(&s_cnt[ucl], 1u);
+    if (p < umax) ws.unit_order[p] = make_uint2((uint32_t)i, nf);
 }
 
 // ------------------------------------------------------------------ K3
@@ -369,7 +376,7 @@ __global__ void __launch_bounds__(256) k_scatter(GsrDims d, Ptrs ws)
     const int v = blockIdx.y;
     const bool live = g < d.G;
     const size_t vg = (size_t)v * d.G + (live ? g : 0);
-    const float4 q0 = reinterpret_cast<const float4 *>(ws.records + vg)[0];
+    const float4 q0 = ws.geo[vg];
     const int rad = live ? (int)(__float_as_uint(q0.w) & 0xffffffu) : 0;
     const int gx = tiles_x(d.W), gy = tiles_y(d.H), T = gx * gy;
     int minx = 0, miny = 0, maxx = 0, maxy = 0;
@@ -401,7 +408,7 @@ __global__ void __launch_bounds__(256) k_scatter_lds(GsrDims d, Ptrs ws)
     const int v = blockIdx.y;
     const bool live = g < d.G;
     const size_t vg = (size_t)v * d.G + (live ? g : 0);
-    const float4 q0 = reinterpret_cast<const float4 *>(ws.records + vg)[0];
+    const float4 q0 = ws.geo[vg];
     const int rad = live ? (int)(__float_as_uint(q0.w) & 0xffffffu) : 0;
     const int gx = tiles_x(d.W), gy = tiles_y(d.H), T = gx * gy;
     uint32_t *s_cnt = s_sc, *s_base = s_sc + T;
@@ -922,6 +929,9 @@ int layout(const GsrDims &d, long long cap, GsrLayout &L)
     L.final_C = take(seg == SEG_ONE ? 0 : V * P * 16);
     L.ckpt = take(ckpt_slots(cap, seg) * CKPT_SLOT_FLOATS * 4);
     L.unit_order = take(unit_capacity(V * T, cap, seg) * 8);
+    L.geo = take(V * d.G * 16);
+    L.opac = take((size_t)d.B * d.G * 4);
+    L.scan = take(scan_words(V * T) * 4);
     L.total = off;
     return GSR_OK;
 }
@@ -948,6 +958,9 @@ Ptrs carve(void *base, const GsrLayout &L)
     w.final_C = reinterpret_cast<float4 *>(p + L.final_C);
     w.ckpt = reinterpret_cast<float *>(p + L.ckpt);
     w.unit_order = reinterpret_cast<uint2 *>(p + L.unit_order);
+    w.geo = reinterpret_cast<float4 *>(p + L.geo);
+    w.opac = reinterpret_cast<float *>(p + L.opac);
+    w.scan = reinterpret_cast<uint32_t *>(p + L.scan);
     return w;
 }
 
@@ -990,8 +1003,12 @@ int forward(const GsrDims &d, const GsrView *views, const float *means, const fl
     tm.end(GSR_STAGE_PREPROCESS); tm.begin(GSR_STAGE_SCAN);
     {
         const uint32_t seg = seg_len(d);
-        hipLaunchKernelGGL(k_scan_tiles, dim3(1), dim3(1024), 0, stream, V * T, cap, ws, status, persistent_counters ? 1 : 0, mse_target ? V + 1 : 0,
-                           seg, (uint32_t)unit_capacity((size_t)V * T, cap, seg));
+        const int n = V * T;
+        const dim3 gS((n + SCAN_CHUNK - 1) / SCAN_CHUNK);
+        hipLaunchKernelGGL(k_scan_partials, gS, dim3(SCAN_CHUNK), 0, stream, n, ws, mse_target ? V + 1 : 0, seg);
+        hipLaunchKernelGGL(k_scan_offsets, gS, dim3(SCAN_CHUNK), 0, stream, n, cap, ws, status, seg);
+        hipLaunchKernelGGL(k_scan_place, gS, dim3(SCAN_CHUNK), 0, stream, n, cap, ws, persistent_counters ? 1 : 0, seg,
+                           (uint32_t)unit_capacity((size_t)V * T, cap, seg));
     }
     tm.end(GSR_STAGE_SCAN);
     if (bin) return launch_status();  // status is final here: the host can size / retry before the heavy stages
