@@ -27,23 +27,33 @@ def _same_bits(a, b):
 
 def _z_rows(B, N, seed):
     """|gt| exact in fp32 whatever the operation order: points on the z axis.  Rows: random, quantised to 1/8 (heavy ties), all equal,
-    one NaN, random again (B = 1: the random row only)."""
+    one NaN, random with three points of |gt| = 0 and (N >= 1536) one of |gt| = +inf -- key 0 and key 0x7f800000, the two ends of the radix
+    range; the inf has no NaN component and lies above the 99.8 % rank (B = 1: the random row only)."""
     g = torch.Generator().manual_seed(seed)
     z = (torch.randn(B, N, generator=g) * 2).abs() + 0.01
     if B >= 4:
         z[1] = (z[1] * 8).round() / 8
         z[2] = 1.25
         z[3, N // 3] = float("nan")
+        z[4, [1, N // 2, N - 1]] = 0.0
+        if N >= 1536:
+            z[4, N // 5] = float("inf")
     sign = torch.where(torch.rand(B, N, generator=g) < 0.5, -1.0, 1.0)
     return z, torch.stack((torch.zeros_like(z), torch.zeros_like(z), z * sign), dim=-1)
 
 
 @pytest.mark.parametrize("B", [1, 5])
-@pytest.mark.parametrize("N", [256, 501, 1536, 65536])       # r < 1 (lo = 0); both ranks integral (w == 0); one workgroup per map; several per map
+# r < 1 (lo = 0); both ranks integral (w == 0); one workgroup per map; 8 192: the last size on one workgroup, every register slot full; 8 193: the
+# first on several (9 chunks of 911: the last 256-lane step of a chunk has dead lanes); 40 001 (B = 5: 40 chunks of 1 001); 65 536: whole chunks
+@pytest.mark.parametrize("N", [256, 501, 1536, 8192, 8193, 40001, 65536])
 def test_selection_is_exact(N, B):
     from styl3r_amd._lib import GSR_PT_NAN
     d1, gt1 = _z_rows(B, N, 10 + N)
     d2, gt2 = _z_rows(B, N, 20 + N)
+    if B >= 4:
+        for d, gt in ((d1, gt1), (d2, gt2)):
+            assert int((d[4] == 0).sum()) == 3 and int(torch.isinf(d[4]).sum()) == (1 if N >= 1536 else 0) and not torch.isnan(gt[4]).any()
+            assert torch.isfinite(torch.quantile(d[4], Q)).all()          # the yardstick's own row is finite: the inf lies above the 99.8 % rank
     conf = torch.full((B, N), 5.0)
     loss, det = _hip(gt1.to(DEV), gt2.to(DEV), (gt1 + 0.1).nan_to_num(0.0).to(DEV), (gt2 - 0.1).nan_to_num(0.0).to(DEV), conf.to(DEV), conf.to(DEV))
     want = torch.stack((torch.quantile(d1, Q, dim=1).t(), torch.quantile(d2, Q, dim=1).t()))        # (2, B, 2)
