@@ -355,6 +355,62 @@ int gsr_regr3d_bwd(const float *gt1, const float *gt2, const float *pr1, const f
                    float *grad_pr1, float *grad_pr2, void *stream);
 
 /*
+ * Scene outputs (csrc/gsr_outputs.hip): the cameras of a fly-through video, the video as bytes and the vertex table of a .ply export
+ * (src/visualization/camera_trajectory/{interpolation,wobble}.py, src/misc/utils.py::vis_depth_map, src/visualization/layout.py,
+ * src/model/ply_export.py).  Device pointers only, nothing syncs with the host, no float atomics, two runs give the same bits.
+ * scratch: gsr_outputs_scratch_bytes() of device memory, uninitialised, for depth_range and ply_normalizer.
+ *
+ * trajectory: P endpoint pairs c2w_a, c2w_b (P,4,4), K_a, K_b (P,3,3), t (F) -> c2w (P,F,4,4), K (P,F,3,3).
+ *     tm = t * t_scale + t_shift, formed in fp32 (the exaggerated video's t * 5 - 2; outside [0, 1] is legal).
+ *     c2w = interpolate_extrinsics(A, B, tm, eps): look vectors a, b = third columns, parallel iff ||a.b| - 1| < eps; pivot = midpoint of
+ *       the origins if parallel, else the least-squares intersection of the look rays; pivot frame [y x z, y, z] with z = a,
+ *       y = normalize(a x b') and b' = b, replaced by (0,0,1) and then (0,1,0) while parallel to a; per endpoint 3 translations in
+ *       [y x look, y, look] and the Y and Z angles of the intrinsic "YXZ" Euler decomposition of frame^T R (X dropped; at gimbal lock the
+ *       third angle is 0); translations linear, angles by interpolate_circular (mod 2 pi, shorter way, the reference's tie rules);
+ *       back through pivot_parameters_to_extrinsics.  float64 throughout, ONE rounding to fp32 (the reference rounds before the last step).
+ *     K = K_a + (K_b - K_a) * tm in fp32, bit-identical to interpolate_intrinsics.
+ *     hold_a: pose and intrinsics of A for every frame.
+ *     wobble_factor != 0: c2w is right-multiplied by the transform with tf[0,3] = sin(2 pi n t) r, tf[1,3] = -cos(2 pi n t) r on the
+ *       UNMAPPED t, n = wobble_rotations, r = wobble_factor * (wobble_radius ? wobble_radius[p] : |o_a - o_b|), times t if
+ *       wobble_scale_with_t.  wobble_radius: NULL or device fp32 [P].
+ *   Finite orthonormal inputs never give a NaN.
+ *
+ * depth_range: over the first min(n, max_elems) depths in flat order, range[1] = far = log(q_0.99 of all), range[0] = near =
+ *     log(q_0.01 of the positive ones), both with torch.quantile's linear interpolation (radix selection, no sort), the logarithm
+ *     correctly rounded; range[2], range[3] = the two quantiles themselves.  status[0] = count of positive depths, status[1] =
+ *     GSR_DEPTH_NO_POSITIVE if there is none, and then near = 0 (the reference's except branch).  A NaN depth makes far NaN.
+ *   Deviation from the reference: the positive set is "the positives among the first max_elems elements", the reference's is "the first
+ *   max_elems positives"; the two differ only above max_elems (16 000 000 there) depths.
+ *
+ * pack_frames: n_panels <= 4 panels of F frames, each planar RGB (F,3,H,W) or, where is_depth[i] != 0, a depth (F,H,W), device fp32,
+ *     contiguous; `panels` and `is_depth` are HOST arrays.  out: uint8 (F', H_out, W_out, 3), pixel-interleaved.  Panels follow each other
+ *     along axis (0: rows, vcat; 1: columns, hcat) with `gap` pixels of value 255 between them; loop_reverse appends frames F-2 .. 1,
+ *     F' = F + max(F - 2, 0).  RGB byte = uint8(clip(x, 0, 1) * 255), truncating, the product in fp32 (NaN -> 0).  Depth:
+ *     x = 1 - (log d - near) / (far - near) with range = (near, far) on the device; NaN -> black, else turbo[min(int(clip(x,0,1) * 256), 255)]
+ *     (matplotlib's 256 nodes as bytes, csrc/gsr_turbo_lut.h).  One streaming launch; a lane writes 4 pixels as 3 dwords.
+ *
+ * ply_normalizer: export_ply(shift_and_scale=True): out[0..2] = torch.median's lower median of means (G,3) per axis, out[3] = max over
+ *     axes of the 95 % quantile of |means - median|; G >= 2.
+ * ply_rows: rows (G, 17 + n_rest) fp32 in construct_list_of_attributes order: x y z, nx ny nz (0), f_dc_0..2, f_rest_* (unless
+ *     dc_only; n_rest = 3 (d_sh - 1), index c (d_sh - 1) + k - 1 for harmonics[g][c][k]), opacity (raw), scale_0..2 = log(scales),
+ *     rot_0..3 = (w,x,y,z) of scipy's from_quat(xyzw).as_matrix() -> from_matrix().as_quat() round trip in float64, rounded once.
+ *     normalizer: NULL, or the 4 floats of ply_normalizer: then (means - median) / factor and log(scales / factor).
+ * GSR_EINVAL before any launch: null pointers, P, F, n, G, H, W, d_sh < 1 (ply_normalizer: G < 2), n_panels outside 1..4, axis outside
+ * {0, 1}, gap < 0, eps <= 0, a depth panel without range.
+ */
+#define GSR_DEPTH_NO_POSITIVE 1
+int gsr_trajectory(const float *c2w_a, const float *c2w_b, const float *K_a, const float *K_b, const float *t, int P, int F, float t_scale,
+                   float t_shift, float eps, int hold_a, float wobble_factor, int wobble_rotations, int wobble_scale_with_t,
+                   const float *wobble_radius, float *c2w, float *K, void *stream);
+size_t gsr_outputs_scratch_bytes(void);
+int gsr_depth_range(const float *depth, int64_t n, int64_t max_elems, void *scratch, float *range, int32_t *status, void *stream);
+int gsr_pack_frames(const float *const *panels, const int32_t *is_depth, int n_panels, int F, int H, int W, int axis, int gap,
+                    int loop_reverse, const float *range, uint8_t *out, void *stream);
+int gsr_ply_normalizer(const float *means, int64_t G, void *scratch, float *out, void *stream);
+int gsr_ply_rows(const float *means, const float *scales, const float *rotations, const float *harmonics, const float *opacities, int64_t G,
+                 int d_sh, int dc_only, const float *normalizer, float *rows, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

@@ -18,8 +18,8 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip"]
-_HEADERS = ["gsr_common.h", "../../include/gsr.h"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip"]
+_HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -117,12 +117,14 @@ GSR_ST_UNITS = 4
 GSR_VIEW_FLOATS = 64
 GSR_N_STAGES = 7
 GSR_PT_EMPTY_MAP, GSR_PT_NAN, GSR_PT_EMPTY_VIEW = 1, 2, 4     # status bits of gsr_regr3d_fwd
+GSR_DEPTH_NO_POSITIVE = 1                                     # status[1] of gsr_depth_range
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_fused", "gsr_backward_fused", "gsr_version", "gsr_profile_create",
            "gsr_profile_destroy", "gsr_profile_read", "gsr_profile_set_stages", "gsr_last_error", "gsr_build_views", "gsr_mse_scratch_bytes",
            "gsr_mse_forward", "gsr_mse_backward", "gsr_image_scores_scratch_bytes", "gsr_image_scores", "gsr_pose_adam_update", "gsr_forward_styles", "gsr_styles_extra_bytes",
            "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_ransac", "gsr_ssim_structure_scratch_bytes", "gsr_ssim_structure_fwd", "gsr_ssim_structure_bwd",
-           "gsr_pointmap_post", "gsr_regr3d_scratch_bytes", "gsr_regr3d_fwd", "gsr_regr3d_bwd")
+           "gsr_pointmap_post", "gsr_regr3d_scratch_bytes", "gsr_regr3d_fwd", "gsr_regr3d_bwd",
+           "gsr_trajectory", "gsr_outputs_scratch_bytes", "gsr_depth_range", "gsr_pack_frames", "gsr_ply_normalizer", "gsr_ply_rows")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -193,6 +195,19 @@ def load() -> C.CDLL:
     lib.gsr_regr3d_fwd.restype = C.c_int
     lib.gsr_regr3d_bwd.argtypes = [vp, vp, vp, vp, i64, i64, C.c_int, i64, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.gsr_regr3d_bwd.restype = C.c_int
+    f32 = C.c_float
+    lib.gsr_trajectory.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, C.c_int, f32, C.c_int, C.c_int, vp, vp, vp, vp]
+    lib.gsr_trajectory.restype = C.c_int
+    lib.gsr_outputs_scratch_bytes.argtypes = []
+    lib.gsr_outputs_scratch_bytes.restype = C.c_size_t
+    lib.gsr_depth_range.argtypes = [vp, i64, i64, vp, vp, vp, vp]
+    lib.gsr_depth_range.restype = C.c_int
+    lib.gsr_pack_frames.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    lib.gsr_pack_frames.restype = C.c_int
+    lib.gsr_ply_normalizer.argtypes = [vp, i64, vp, vp, vp]
+    lib.gsr_ply_normalizer.restype = C.c_int
+    lib.gsr_ply_rows.argtypes = [vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, vp, vp, vp]
+    lib.gsr_ply_rows.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

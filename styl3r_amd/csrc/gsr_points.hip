@@ -22,6 +22,7 @@
 
 #include "../../include/gsr.h"
 #include "gsr_common.h"
+#include "gsr_select.h"
 
 namespace gsr {
 
@@ -29,7 +30,6 @@ namespace gsr {
 #pragma clang fp contract(off)
 
 constexpr int PT_BLOCK = 256, PT_MAX_CHUNKS = 64;
-constexpr int SEL_BINS = 256, SEL_RANKS = 4, SEL_PASSES = 4;
 constexpr int SEL_ONE_BLOCK = 1024, SEL_ONE_KEYS = 8;
 constexpr long long SEL_ONE_MAX_N = (long long)SEL_ONE_BLOCK * SEL_ONE_KEYS;
 constexpr float CONF_MIN = 3.0f;
@@ -85,55 +85,11 @@ __device__ inline float pt_dis(const float *__restrict__ p)
 }
 __device__ inline uint32_t pt_key(float d) { return __float_as_uint(d) & 0x7fffffffu; }    // (a NaN sorts behind +inf; the map's flag overrides the result)
 
-// the four ranks torch.quantile reads for q = 0.002 and 0.998: floor / ceil of float32(q) * float32(N - 1)
+// the four ranks torch.quantile reads for q = 0.002 and 0.998
 __device__ inline void sel_ranks(long long N, uint32_t *k, float *w)
 {
-    const float pos[2] = {0.002f * (float)(N - 1), 0.998f * (float)(N - 1)};
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const float lo = floorf(pos[q]);
-        k[2 * q] = (uint32_t)lo;
-        k[2 * q + 1] = (uint32_t)ceilf(pos[q]);
-        w[q] = pos[q] - lo;
-    }
-}
-// torch's lerp(a, b, w)
-__device__ inline float sel_lerp(float a, float b, float w) { return w < 0.5f ? a + w * (b - a) : b - (b - a) * (1.0f - w); }
-
-// every valid lane bumps h[digit]: one LDS atomic per DISTINCT digit of the wavefront (pass 0 sees the exponent byte: two or three values)
-__device__ inline void hist_bump_grouped(uint32_t *h, uint32_t digit, bool valid)
-{
-    const int lane = threadIdx.x & 63;
-    unsigned long long todo = __ballot(valid);
-    while (todo) {
-        const int leader = __ffsll((long long)todo) - 1;
-        const uint32_t dl = (uint32_t)__builtin_amdgcn_readlane((int)digit, leader);
-        const unsigned long long m = __ballot(valid && digit == dl);
-        if (lane == leader) atomicAdd(h + dl, (uint32_t)__popcll(m));
-        todo &= ~m;
-    }
-}
-
-// one digit of one rank, by ONE wavefront: the bin of `h[256]` that holds rank k (0-based among the counted keys); returns the digit and
-// leaves in k the rank inside that bin.  Same result in every lane.
-__device__ inline uint32_t sel_pick(const uint32_t *h, uint32_t &k)
-{
-    const int lane = threadIdx.x & 63;
-    const uint32_t c0 = h[4 * lane], c1 = h[4 * lane + 1], c2 = h[4 * lane + 2], c3 = h[4 * lane + 3];
-    const uint32_t s = c0 + c1 + c2 + c3;
-    uint32_t incl = s;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = (uint32_t)__shfl_up((int)incl, o, 64);
-        if (lane >= o) incl += t;
-    }
-    const uint32_t excl = incl - s;
-    const unsigned long long hit = __ballot(excl <= k && k < incl);
-    const int src = hit ? __ffsll((long long)hit) - 1 : 63;          // (no hit: k beyond the count, cannot happen with every key counted)
-    uint32_t r = k - excl, d = 4 * lane;
-    if (r >= c0) { r -= c0; ++d; if (r >= c1) { r -= c1; ++d; if (r >= c2) { r -= c2; ++d; } } }
-    k = (uint32_t)__shfl((int)r, src, 64);
-    return (uint32_t)__shfl((int)d, src, 64);
+    sel_rank_pair(0.002f, N, k, w);
+    sel_rank_pair(0.998f, N, k + 2, w + 1);
 }
 
 __device__ inline void sel_finish(const uint32_t *prefix, const float *w, bool nan, float *q)

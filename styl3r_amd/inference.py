@@ -5,19 +5,23 @@ The reference calls the encoder once with the first context image as "identity" 
 poses on the un-stylized Gaussians, then renders the plain and every stylized set through the same cameras, one rasterizer pass per
 (set, camera list).  Here the style-independent part of the encoder runs once (`encode_scene`), all styles of one image size go
 through ONE `restyle` batch, and the plain + S stylized sets -- which share means, covariances and opacities -- are rendered by ONE
-`forward_styles` call.  Trajectory interpolation, video / PLY files and the dataset readers stay with the caller: the function takes
-cameras, so a video is a call whose target holds the 60 interpolated extrinsics.
+`forward_styles` call.  `render_flythrough` turns the result into the frames of the drivers' videos (render_video_generic and the
+wrapper's three trajectories) and `export_scene_ply` into their .ply files; encoding a container and the dataset readers stay with the
+caller.
 """
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from pathlib import Path
+from typing import Optional, Sequence, Union
 
 import torch
 from torch import Tensor
 
 from .decoder import DecoderOutput, Gaussians
 from .evaluation import TestCfg, align_target_poses
+from .export import depth_range, export_ply, pack_frames
+from .trajectory import KINDS, trajectory_cameras
 
 
 @dataclass
@@ -81,3 +85,75 @@ def stylize_scene(encoder, decoder, context: dict, styles, target: dict, *, alig
         out: DecoderOutput = decoder.forward_styles(plain, [g.harmonics for g in gaussians], extrinsics, target["intrinsics"],
                                                     target["near"], target["far"], (h, w))
     return StylizedScene(gaussians, extrinsics, out.color, out.depth, dump)
+
+
+def _panel_set(name, n_sets: int) -> int:
+    """panel name -> index into [plain, style 0, style 1, ...]; -1 for the depth"""
+    if name == "depth":
+        return -1
+    if isinstance(name, bool) or not (isinstance(name, int) or name in ("plain", "stylized")):
+        raise ValueError(f"unknown panel {name!r}: 'plain', 'depth', 'stylized' or an integer style index")
+    i = 0 if name == "plain" else (1 if name == "stylized" else 1 + name)
+    if not 0 <= i < n_sets:
+        raise ValueError(f"panel {name!r} asks for Gaussian set {i} of {n_sets} ([plain, style 0, ...])")
+    return i
+
+
+def render_flythrough(decoder, scene_or_gaussians: Union[StylizedScene, Gaussians, Sequence[Gaussians]], context: dict,
+                      target: Optional[dict] = None, kind: str = "interpolation", num_frames: Optional[int] = None,
+                      smooth: Optional[bool] = None, loop_reverse: Optional[bool] = None, panels: Sequence = ("stylized",), axis: int = 0,
+                      gap: int = 8, frames_per_pass: int = 60) -> Tensor:
+    """The frames of one of the drivers' videos as bytes: uint8 (F', H_out, W_out, 3) on the device.
+      scene_or_gaussians  a `StylizedScene`, or its list [plain, style 0, ...] of `Gaussians` over one geometry, or one `Gaussians`
+      context / target    as `trajectory_cameras` takes them (context also gives the image size and near / far); b == 1
+      kind                "interpolation", "wobble" or "interpolation_exaggerated"; num_frames / smooth / loop_reverse default to the
+                          reference's for that kind (60 eased looped frames; exaggerated: 300, linear, no loop)
+      panels              up to 4 of "plain", "depth", "stylized" (= style 0) or an integer style index, laid out along `axis` with `gap`
+    One `gsr_trajectory` launch, one `forward_styles` pass over the sets the panels name per `frames_per_pass` cameras (the rasterizer's
+    workspace is sized for one pass, not for the video), `depth_range` over the whole video if a depth panel is asked for, and one
+    `pack_frames`.  Nothing is copied to the host."""
+    if isinstance(scene_or_gaussians, StylizedScene):
+        sets = list(scene_or_gaussians.gaussians)
+    elif isinstance(scene_or_gaussians, Gaussians):
+        sets = [scene_or_gaussians]
+    else:
+        sets = list(scene_or_gaussians)
+    if context["image"].shape[0] != 1:
+        raise ValueError("render_flythrough serves one scene per call (b == 1), as the reference's inference drivers do")
+    if not 1 <= len(panels) <= 4 or frames_per_pass < 1:
+        raise ValueError("render_flythrough takes 1 to 4 panels and frames_per_pass >= 1")
+    which = [_panel_set(p, len(sets)) for p in panels]
+    used = sorted({i for i in which if i >= 0}) or [0]
+    extrinsics, intrinsics, near, far = trajectory_cameras(context, target, kind, num_frames, smooth)
+    F = extrinsics.shape[1]
+    h, w = context["image"].shape[-2:]
+    dev = extrinsics.device
+    color = torch.empty((len(used), F, 3, h, w), dtype=torch.float32, device=dev)
+    depth = torch.empty((F, h, w), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for f0 in range(0, F, frames_per_pass):
+            f1 = min(F, f0 + frames_per_pass)
+            out = decoder.forward_styles(sets[0], [sets[i].harmonics for i in used], extrinsics[:, f0:f1], intrinsics[:, f0:f1],
+                                         near[:, f0:f1], far[:, f0:f1], (h, w))
+            color[:, f0:f1] = out.color[:, 0]
+            depth[f0:f1] = out.depth[0]
+    tensors = [depth if i < 0 else color[used.index(i)] for i in which]
+    rng = depth_range(depth) if -1 in which else None
+    return pack_frames(tensors, axis=axis, gap=gap, loop_reverse=KINDS[kind][2] if loop_reverse is None else loop_reverse, depth_range=rng)
+
+
+def export_scene_ply(scene: StylizedScene, directory, shift_and_scale: bool = False, save_sh_dc_only: bool = True) -> list:
+    """infer_model_re10k.py:542-557: `gaussians.ply` for the un-stylized set and `stylized_gaussians.ply` for the stylized one
+    (`stylized_gaussians_<s>.ply` per style when the scene holds several), scales and rotations from the visualization dump.
+    Returns the paths written."""
+    directory = Path(directory)
+    dump = scene.visualization_dump
+    scales, rotations = dump["scales"][0].reshape(-1, 3), dump["rotations"][0].reshape(-1, 4)
+    n_styles = len(scene.gaussians) - 1
+    paths = []
+    for i, g in enumerate(scene.gaussians):
+        name = "gaussians.ply" if i == 0 else ("stylized_gaussians.ply" if n_styles == 1 else f"stylized_gaussians_{i - 1}.ply")
+        export_ply(g.means[0], scales, rotations, g.harmonics[0], g.opacities[0], directory / name, shift_and_scale=shift_and_scale,
+                   save_sh_dc_only=save_sh_dc_only)
+        paths.append(directory / name)
+    return paths
