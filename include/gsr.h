@@ -85,6 +85,9 @@ typedef struct GsrDims {
                                     after the forward only: the backward leaves the accumulators dirty. */
 #define GSR_FLAG_BIN_BALLOT 32    /* K1 / K3 bin with wave-aggregated global atomics (the path of images beyond 4 096 tiles per view) even where
                                     the per-workgroup LDS histograms apply: A/B runs and the equivalence test */
+#define GSR_FLAG_K6_SWAP_SUM 64   /* gsr_backward without a depth gradient: the composite backward sums its nine per-splat partials with the two
+                                    permlane-swap levels (the form before the LDS transpose, and still the one of the depth-gradient kernel)
+                                    instead of through the LDS: A/B runs and the parity test.  Same sums up to the order of a 64-term fp32 add */
 #define GSR_FLAG_SORT_KEYS_SHIFT 8   /* bits 8-9: LDS budget of the per-tile depth sort: 0 = 4096 keys (default), 1 = 1024,
                                        2 = 2048.  Pick the smallest budget >= the longest per-tile list expected
                                        (status[GSR_ST_MAX_TILE] of an earlier call): more workgroups fit a CU.  Longer lists
@@ -208,6 +211,18 @@ int gsr_backward_fused(const GsrDims *dims, const GsrView *views, const float *m
                        const float *dL_dimage, const float *dL_ddepth, float *dL_dmeans, float *dL_dcov6,
                        float *dL_dopac, float *dL_dshs, float *dL_dmeans2D, float *dL_dtau, const GsrFused *fx,
                        void *stream);
+
+/*
+ * The composite backward's nine-value wave reduction on its own.  variant 0: the LDS transpose (default of the depth-free kernel),
+ * 1: the permlane-swap form (GSR_FLAG_K6_SWAP_SUM).
+ *   gsr_k6_blocks_per_cu  hipOccupancyMaxActiveBlocksPerMultiprocessor of the depth-free composite backward (64 threads, its static LDS);
+ *                         negative: GSR_ELAUNCH
+ *   gsr_test_reduce9      test entry: `blocks` single-wave workgroups, each runs `rounds` reductions back to back as the kernel does on
+ *                         consecutive (tile, splat) pairs.  in: device fp32 (blocks, rounds, 9, 64), value i of lane l; out: device fp32
+ *                         (blocks, rounds, 9), the totals, each stored by the lane the variant's slot map names.
+ */
+int gsr_k6_blocks_per_cu(int variant);
+int gsr_test_reduce9(const float *in, float *out, int rounds, int blocks, int variant, void *stream);
 
 /*
  * Multi-style forward (inference): S Gaussian sets that share means / covariances / opacities and differ only in colour, rendered

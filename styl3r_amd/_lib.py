@@ -107,6 +107,7 @@ GSR_FLAG_PHASE_BIN = 4
 GSR_FLAG_PHASE_RENDER = 8
 GSR_FLAG_PREZERO_GRADS = 16
 GSR_FLAG_BIN_BALLOT = 32
+GSR_FLAG_K6_SWAP_SUM = 64    # composite backward, no depth gradient: permlane-swap reduction instead of the LDS transpose (A/B, parity test)
 GSR_ID_MASK = 0x0FFFFFFF
 GSR_QUAD_SHIFT = 28
 GSR_FLAG_SORT_KEYS_SHIFT = 8
@@ -124,6 +125,7 @@ EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_f
            "gsr_mse_forward", "gsr_mse_backward", "gsr_image_scores_scratch_bytes", "gsr_image_scores", "gsr_pose_adam_update", "gsr_forward_styles", "gsr_styles_extra_bytes",
            "gsr_pnp_ransac_scratch_bytes", "gsr_pnp_ransac", "gsr_ssim_structure_scratch_bytes", "gsr_ssim_structure_fwd", "gsr_ssim_structure_bwd",
            "gsr_pointmap_post", "gsr_regr3d_scratch_bytes", "gsr_regr3d_fwd", "gsr_regr3d_bwd",
+           "gsr_k6_blocks_per_cu", "gsr_test_reduce9",
            "gsr_trajectory", "gsr_outputs_scratch_bytes", "gsr_depth_range", "gsr_pack_frames", "gsr_ply_normalizer", "gsr_ply_rows")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
@@ -195,6 +197,10 @@ def load() -> C.CDLL:
     lib.gsr_regr3d_fwd.restype = C.c_int
     lib.gsr_regr3d_bwd.argtypes = [vp, vp, vp, vp, i64, i64, C.c_int, i64, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.gsr_regr3d_bwd.restype = C.c_int
+    lib.gsr_k6_blocks_per_cu.argtypes = [C.c_int]
+    lib.gsr_k6_blocks_per_cu.restype = C.c_int
+    lib.gsr_test_reduce9.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]
+    lib.gsr_test_reduce9.restype = C.c_int
     f32 = C.c_float
     lib.gsr_trajectory.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, f32, f32, f32, C.c_int, f32, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.gsr_trajectory.restype = C.c_int

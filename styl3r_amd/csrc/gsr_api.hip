@@ -125,6 +125,38 @@ __global__ void k_build_views(const float *__restrict__ c2w, const float *__rest
     for (int i = 0; i < 7; ++i) o.pad[i] = 0.f;
 }
 #pragma clang fp contract(fast)
+
+// ------------------------------------------------------------------ the composite backward's nine-value reductions on their own
+// (here and not beside K6: tests/test_host_boundary.py counts the swaps of gsr_backward.hip)
+// `rounds` reductions back to back per single-wave workgroup, as K6 runs them on consecutive (tile, splat) pairs: in[block][round][9][64],
+// out[block][round][9], each total stored by the lane the slot map names
+template <bool LDS_SUM>
+__global__ void __launch_bounds__(64) k_test_reduce9(const float *__restrict__ in, float *__restrict__ out, int rounds)
+{
+    __shared__ __attribute__((aligned(16))) float s_red[LDS_SUM ? 8 * 64 : 4];
+    const int lane = threadIdx.x;
+    const int slot = LDS_SUM ? reduce9_lds_slot(lane) : reduce9_slot(lane);
+    in += (size_t)blockIdx.x * rounds * 9 * 64;
+    out += (size_t)blockIdx.x * rounds * 9;
+    for (int r = 0; r < rounds; ++r) {
+        float v[9];
+#pragma unroll
+        for (int i = 0; i < 9; ++i) v[i] = in[((size_t)r * 9 + i) * 64 + lane];
+        float val;
+        if constexpr (LDS_SUM) val = wave_reduce9_lds(v, s_red, lane);
+        else val = wave_reduce9(v);
+        if (slot >= 0) out[(size_t)r * 9 + slot] = val;
+    }
+}
+
+int test_reduce9(const float *in, float *out, int rounds, int blocks, int variant, hipStream_t stream)
+{
+    if (!in || !out || rounds <= 0 || blocks <= 0 || (variant != 0 && variant != 1)) return GSR_EINVAL;
+    (void)hipGetLastError();
+    if (variant == 0) hipLaunchKernelGGL(k_test_reduce9<true>, dim3(blocks), dim3(64), 0, stream, in, out, rounds);
+    else hipLaunchKernelGGL(k_test_reduce9<false>, dim3(blocks), dim3(64), 0, stream, in, out, rounds);
+    return launch_status();
+}
 }  // namespace gsr
 
 extern "C" {
@@ -184,6 +216,13 @@ __attribute__((visibility("default"))) int gsr_backward_fused(const GsrDims *dim
     if (!dims) return GSR_EINVAL;
     return gsr::backward(*dims, views, means, cov6, shs, pair_capacity, workspace, workspace_bytes, dL_dimage, dL_ddepth,
                          dL_dmeans, dL_dcov6, dL_dopac, dL_dshs, dL_dmeans2D, dL_dtau, fx, static_cast<hipStream_t>(stream));
+}
+
+__attribute__((visibility("default"))) int gsr_k6_blocks_per_cu(int variant) { return gsr::k6_blocks_per_cu(variant); }
+
+__attribute__((visibility("default"))) int gsr_test_reduce9(const float *in, float *out, int rounds, int blocks, int variant, void *stream)
+{
+    return gsr::test_reduce9(in, out, rounds, blocks, variant, static_cast<hipStream_t>(stream));
 }
 
 __attribute__((visibility("default"))) int gsr_build_views(const float *c2w, const float *K, const float *near,

@@ -9,8 +9,9 @@
 //                       the forward left in the top bits of the list word rides along), then the
 //                       wave evaluates the batch from LDS broadcasts as straight-line code under
 //                       scalar lane masks; each splat's nine (ten with a depth gradient) partial
-//                       gradients are summed across the 64 lanes in registers (permlane swaps +
-//                       bank-packed DPP row sums, no LDS) and leave the wave as ONE atomic
+//                       gradients are summed across the 64 lanes (nine: an LDS transpose of eight
+//                       of them + bank-packed DPP row sums, round 17; ten, or nine under
+//                       GSR_FLAG_K6_SWAP_SUM: permlane swaps + the same row sums, no LDS) and leave the wave as ONE atomic
 //                       instruction per (tile, splat), one lane per component.  Optional
 //                       prologue: dL/dimage of the fused LossMse from the forward's image.  (upstream R7)
 //   K7 preprocess_bwd   per Gaussian, loops over the scene's views and sums their
@@ -31,12 +32,14 @@ enum { GR_RGB = 0, GR_DEPTH = 3, GR_MX = 4, GR_MY = 5, GR_CA = 6, GR_CB = 7, GR_
 // ------------------------------------------------------------------ K6
 // One wavefront per tile, 4 pixels per lane (same pixel <-> lane map as the forward).
 // A lane first adds the partial gradients of its own pixels in registers, then ONE
-// ten-value wave reduction per splat (wave_reduce10) and ten lanes issue the tile's single
-// atomic per component.  No LDS atomics, no workgroup barriers.
+// wave reduction per splat (ten values: wave_reduce10; nine: wave_reduce9_lds, or wave_reduce9 in the swap form) and ten / nine lanes
+// issue the tile's single atomic per component.  No LDS atomics, no workgroup barriers.
 // DEPTH = false: no dL/ddepth was passed (Styl3R trains on colour only): the depth terms drop out of the evaluation
 // MSE: dL/dimage += 2 weight / n * upstream gradient * (image - target), LossMse's backward (loss_mse.py:22-31), formed here from the difference
 // the composite forward left in the workspace (gsr_forward_fused with a target); dL_dimage may then be nullptr (nothing else consumed the image).
-template <bool DEPTH>
+// LDS_SUM (depth-free only, the default of the host entry): the nine sums cross the lanes through an LDS transpose (wave_reduce9_lds, 2 KiB more
+// per workgroup: 5 120 B, still 32 single-wave workgroups per CU) instead of the two swap levels; GSR_FLAG_K6_SWAP_SUM selects the swap form.
+template <bool DEPTH, bool LDS_SUM = false>
 __global__ void __launch_bounds__(64) k_composite_bwd(GsrDims d, const GsrView *__restrict__ views, Ptrs ws,
                                                      const float *__restrict__ dL_dimage,
                                                      const float *__restrict__ dL_ddepth,
@@ -44,7 +47,9 @@ __global__ void __launch_bounds__(64) k_composite_bwd(GsrDims d, const GsrView *
 {
     if (ws.status[GSR_ST_OVERFLOW]) return;
     if (blockIdx.x >= (uint32_t)ws.status[GSR_ST_UNITS]) return;     // the grid is unit_capacity(): units beyond this launch's count
+    static_assert(!(DEPTH && LDS_SUM), "the LDS reduction carries nine values: eight planes and one DPP-only value");
     __shared__ float4 s_q[64 * 3];
+    __shared__ __attribute__((aligned(16))) float s_red[LDS_SUM ? 8 * 64 : 4];      // (referenced by the LDS_SUM instantiation only)
 
     const int gx = tiles_x(d.W), T = gx * tiles_y(d.H);
     const uint2 unit = ws.unit_order[blockIdx.x];    // (view*T + tile, depth segment), longest units are launched first
@@ -126,10 +131,10 @@ __global__ void __launch_bounds__(64) k_composite_bwd(GsrDims d, const GsrView *
             }
         }
     }
-    // DEPTH: ten sums, reduce10; depth-free: the nine live sums go through wave_reduce9 (GR_DEPTH's column of grad_rec keeps its zero)
+    // DEPTH: ten sums, reduce10; depth-free: the nine live sums go through wave_reduce9_lds / wave_reduce9 (GR_DEPTH's column of grad_rec keeps its zero)
     constexpr bool NINE = !DEPTH;
     int slot;                                   // the grad_rec column this lane publishes, -1: none
-    if (NINE) { const int i9 = reduce9_slot(lane); slot = i9 < 0 ? -1 : (i9 < 3 ? i9 : i9 + 1); }      // v = s[0..2], s[4..9]
+    if (NINE) { const int i9 = LDS_SUM ? reduce9_lds_slot(lane) : reduce9_slot(lane); slot = i9 < 0 ? -1 : (i9 < 3 ? i9 : i9 + 1); }      // v = s[0..2], s[4..9]
     else slot = reduce10_slot(lane);
 
     // entries [lo, top) of the sorted list, in batches from the back; slot l of a batch = entry hi-1-l.  Each lane
@@ -220,7 +225,8 @@ __global__ void __launch_bounds__(64) k_composite_bwd(GsrDims d, const GsrView *
             float val;             // the packed register of the reduction: every publishing lane finds its total in its own lane
             if (NINE) {
                 const float v9[9] = {s[0], s[1], s[2], s[4], s[5], s[6], s[7], s[8], s[9]};
-                val = wave_reduce9(v9);
+                if constexpr (LDS_SUM) val = wave_reduce9_lds(v9, s_red, lane);
+                else val = wave_reduce9(v9);
             } else {
                 val = wave_reduce10(s);
             }
@@ -525,7 +531,9 @@ int backward(const GsrDims &d, const GsrView *views, const float *means, const f
         // one wavefront per work unit; the unit count is on the device only (status word GSR_ST_UNITS): a grid of its bound, the rest exit
         const dim3 grid((uint32_t)unit_capacity((size_t)V * T, cap, seg_len(d)));
         if (dL_ddepth) hipLaunchKernelGGL(k_composite_bwd<true>, grid, dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
-        else hipLaunchKernelGGL(k_composite_bwd<false>, grid, dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
+        else if (d.flags & GSR_FLAG_K6_SWAP_SUM)
+            hipLaunchKernelGGL((k_composite_bwd<false, false>), grid, dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
+        else hipLaunchKernelGGL((k_composite_bwd<false, true>), grid, dim3(64), 0, stream, d, views, ws, dL_dimage, dL_ddepth, mse, mw, mg);
     }
     tm.end(GSR_STAGE_COMPOSITE_BWD); tm.begin(GSR_STAGE_PREPROCESS_BWD);
     const dim3 gG((d.G + 255) / 256, d.B);
@@ -535,6 +543,16 @@ int backward(const GsrDims &d, const GsrView *views, const float *means, const f
     });
     tm.end(GSR_STAGE_PREPROCESS_BWD);
     return launch_status();
+}
+
+// ------------------------------------------------------------------ K6's occupancy as the runtime computes it
+// variant 0: the LDS form (the default of the depth-free K6), 1: the swap form (GSR_FLAG_K6_SWAP_SUM)
+int k6_blocks_per_cu(int variant)
+{
+    int n = 0;
+    const hipError_t e = variant == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_composite_bwd<false, true>, 64, 0)
+                                      : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_composite_bwd<false, false>, 64, 0);
+    return hip_ok(e) ? n : GSR_ELAUNCH;
 }
 
 }  // namespace gsr

@@ -113,6 +113,8 @@ int backward(const GsrDims &d, const GsrView *views, const float *means, const f
              long long cap, void *workspace, size_t workspace_bytes, const float *dL_dimage, const float *dL_ddepth,
              float *dL_dmeans, float *dL_dcov6, float *dL_dopac, float *dL_dshs, float *dL_dmeans2D, float *dL_dtau,
              const GsrFused *fx, hipStream_t stream);
+int k6_blocks_per_cu(int variant);
+int test_reduce9(const float *in, float *out, int rounds, int blocks, int variant, hipStream_t stream);
 int forward_styles(const GsrDims &d, int S, const GsrView *views, const float *means, const float *cov6, const float *opac,
                    const float *const *shs, long long cap, void *workspace, size_t workspace_bytes, void *extra, size_t extra_bytes,
                    uint32_t *tile_count, float *image, float *depth, float *opacity, int32_t *radii, int32_t *status, hipStream_t stream);
@@ -502,6 +504,7 @@ __device__ inline uint32_t wave_agg_inc(uint32_t *__restrict__ counters, uint32_
 // Sums nine / ten per-lane values over the 64 lanes: level 1 pairs values with v_permlane32_swap so that each half-wave keeps one value of
 // the pair, level 2 does the same across the 16-lane rows with v_permlane16_swap, level 3 finishes inside the rows with bank-packed DPP adds
 // (rows_packed_sum).  A plain per-value DPP reduction costs 6 DPP adds per value.
+// The depth-free kernel's default since round 17 replaces levels 1 and 2 by a transpose through the LDS (wave_reduce9_lds, at the end of this block).
 // The swaps are the compiler builtins (round 5; inline asm before): the compiler places their wait states (s_nop, never v_nop: one v_nop
 // holds the SIMD's VALU port for ~9.5 ns against 0.55 ns for an s_nop state, profiles/r02_issue_cost.md) and, unlike asm operands tied
 // "+v", they do not force copies of the inputs.  Round 2 saw a hipcc build fold the builtin's result pair r[0] + r[1] into r[0] + r[0];
@@ -587,6 +590,33 @@ __device__ inline int reduce9_slot(int lane)       // index into wave_reduce9's 
     const int r = lane >> 4, s = lane & 15;
     if (s == 0) return (r < 2) ? r : r + 2;        // 0,1,4,5
     if (s == 8) return (r < 2) ? r + 2 : r + 4;    // 2,3,6,7
+    return lane == 63 ? 8 : -1;
+}
+// ---- the same nine sums with the two swap levels done by the LDS (round 17) ------------------------------------------------------------
+// The swap levels are a transpose: eight per-lane values over 64 lanes -> two registers of row-level values.  The swaps and their adds sit
+// on the VALU port, the one K6 is short of; DS instructions issue on another port.  Lane l stores its eight partials as planes
+// s_red[i * 64 + l] (eight conflict-free dword stores from one base register: 4 ds_write2st64_b32), then loads float4 #l and float4 #(64 + l) of
+// the array (2 ds_read_b128, contiguous over the wave): the first is value l >> 4 of lanes 4 (l & 15) .. + 3, the second value 4 + (l >> 4) of
+// the same four lanes.  Three adds each give x and y with, per 16-lane row r, the 16 quarter sums of values r and 4 + r: the inputs of
+// rows_packed_sum, which finishes as above.  Lanes 16r hold v_r, lanes 16r + 8 v_{4+r}, lane 63 v8.  6 adds + 9 DPP adds + 6 DS instructions.
+// s_red: 8 * 64 floats private to the wave.  No barrier and no s_waitcnt vmcnt: a wave's DS instructions execute in order, so the loads see
+// this pair's stores and the next pair's stores come after these loads (a __syncthreads would also drain the gradient atomics in flight).  The
+// compiler is only kept from moving the accesses across each other.  The ninth value stays on DPP: a ninth plane would make a single-wave
+// workgroup of K6 5 376 B of LDS, and 32 of those no longer fit a CU's 160 KiB.
+__device__ inline float wave_reduce9_lds(const float *v, float *s_red, int lane)
+{
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s_red[i * 64 + lane] = v[i];
+    asm volatile("" ::: "memory");
+    const float4 p = reinterpret_cast<const float4 *>(s_red)[lane], q = reinterpret_cast<const float4 *>(s_red)[64 + lane];
+    asm volatile("" ::: "memory");
+    return rows_packed_sum((p.x + p.y) + (p.z + p.w), (q.x + q.y) + (q.z + q.w), v[8], true);
+}
+__device__ inline int reduce9_lds_slot(int lane)   // index into wave_reduce9_lds's nine inputs, else -1
+{
+    const int r = lane >> 4, s = lane & 15;
+    if (s == 0) return r;                          // 0,1,2,3
+    if (s == 8) return r + 4;                      // 4,5,6,7
     return lane == 63 ? 8 : -1;
 }
 
