@@ -426,6 +426,34 @@ int gsr_ply_rows(const float *means, const float *scales, const float *rotations
                  int d_sh, int dc_only, const float *normalizer, float *rows, void *stream);
 
 /*
+ * Scene inputs (csrc/gsr_inputs.hip): decoded frames -> the planar fp32 images of a batch, bit-equal to the reference's per-image
+ * host path (src/dataset/shims/crop_shim.py::rescale -- uint8, PIL's 8-bit Lanczos resize, / 255 -- then center_crop, after the
+ * flip of augmentation_shim.py::reflect_views).
+ *
+ * resample_plan (HOST ONLY, no device call): the plan of one axis, n input samples -> m output samples, in float64 with libm's sin.
+ *     *ksize = 2 ceil(3 max(n / m, 1)) + 1 is always written; bounds and coeffs are both NULL (size query) or both given:
+ *     bounds (m,2) int32 = (first tap, tap count), coeffs (m,ksize) int32 = the normalised Lanczos-3 weights in 22-bit fixed point,
+ *     zero behind the count.  A "device plan" below is these two arrays in one buffer, bounds first: m * (2 + ksize) int32.
+ * resample_crop: N source images of H x W -- uint8 (N,H,W,3) interleaved, or fp32 (N,3,H,W) planar when src_is_f32 (quantised as
+ *     uint8(clip(x * 255, 0, 255)), fp32 product, truncating cast, NaN -> 0) -- are scaled to scaled_h x scaled_w and the window
+ *     (top, left, out_h, out_w) of the scaled image is written as fp32 (N,3,out_h,out_w) = byte / 255.
+ *     plan_x / plan_y: device plans of (W -> scaled_w) / (H -> scaled_h); NULL exactly when that size does not change (the axis is
+ *     then not filtered).  Horizontal pass first, bytes between the passes.  flip: NULL or (N) int32 on the device; image n is read
+ *     mirrored along x (at the source, before the filter) where flip[n] != 0.  Only the window's columns and the rows its vertical
+ *     taps touch are computed.  scratch: resample_scratch_bytes() of device memory (4-byte aligned, uninitialised; 0 for invalid
+ *     dimensions).  flags: 0, or GSR_RESAMPLE_DIRECT (tests: the horizontal pass reads global memory tap by tap, as it does by itself
+ *     when a block's source segment does not fit its LDS; same bytes).  Two launches, no host sync, no atomics.
+ * GSR_EINVAL before any launch: null src / scratch / out, N < 1 or > 21845, a size < 1 or > 2^24, a window outside the scaled image,
+ * a plan that is NULL although the size changes (or given although it does not), unknown flags; GSR_ENOSPACE: scratch too small.
+ */
+#define GSR_RESAMPLE_DIRECT 1
+int gsr_resample_plan(int n, int m, int32_t *ksize, int32_t *bounds, int32_t *coeffs);
+size_t gsr_resample_scratch_bytes(int64_t N, int H, int W, int scaled_h, int scaled_w, int top, int left, int out_h, int out_w);
+int gsr_resample_crop(const void *src, int src_is_f32, int64_t N, int H, int W, const int32_t *plan_x, int scaled_w, const int32_t *plan_y,
+                      int scaled_h, int top, int left, int out_h, int out_w, const int32_t *flip, void *scratch, size_t scratch_bytes,
+                      float *out, int flags, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

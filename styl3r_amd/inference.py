@@ -5,9 +5,15 @@ The reference calls the encoder once with the first context image as "identity" 
 poses on the un-stylized Gaussians, then renders the plain and every stylized set through the same cameras, one rasterizer pass per
 (set, camera list).  Here the style-independent part of the encoder runs once (`encode_scene`), all styles of one image size go
 through ONE `restyle` batch, and the plain + S stylized sets -- which share means, covariances and opacities -- are rendered by ONE
-`forward_styles` call.  `render_flythrough` turns the result into the frames of the drivers' videos (render_video_generic and the
-wrapper's three trajectories) and `export_scene_ply` into their .ply files; encoding a container and the dataset readers stay with the
-caller.
+`forward_styles` call.  `prepare_scene` is the other end: decoded frames and raw cameras in, the (context, styles, target) that
+`stylize_scene` takes out, images rescaled and cropped on the device (inputs.py).  `render_flythrough` turns the result into the frames of the drivers' videos (render_video_generic and the
+wrapper's three trajectories) and `export_scene_ply` into their .ply files; encoding a container, decoding the frames and the
+dataset readers stay with the caller.
+
+    context, styles, target = prepare_scene(frames_u8, K, c2w, [0, 40], range(0, 41, 5), [style_a, style_b], device="cuda")
+    scene = stylize_scene(encoder, decoder, context, styles, target)
+    video = render_flythrough(decoder, scene, context)                      # uint8 frames, on the device
+    export_scene_ply(scene, "out/")
 """
 from __future__ import annotations
 
@@ -21,6 +27,7 @@ from torch import Tensor
 from .decoder import DecoderOutput, Gaussians
 from .evaluation import TestCfg, align_target_poses
 from .export import depth_range, export_ply, pack_frames
+from .inputs import InputCfg, apply_style_image_augmentation, prepare_example
 from .trajectory import KINDS, trajectory_cameras
 
 
@@ -40,6 +47,23 @@ def _style_images(styles) -> list:
     if isinstance(styles, Tensor):
         return list(styles.reshape(-1, *styles.shape[-3:]))
     return [im.reshape(*im.shape[-3:]) for im in styles]
+
+
+def prepare_scene(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, context_indices, target_indices, styles, cfg: Optional[InputCfg] = None,
+                  *, pixel_intrinsics: bool = False, scene: str = "", device=None):
+    """Decoded frames + raw cameras of one scene -> (context, styles, target) as `stylize_scene` takes them (b == 1), following
+    infer_model_colmap.py:513-589: `inputs.prepare_example` at stage "test" (no augmentation; the gates raise `inputs.SkipExample`).
+      frames   uint8 (n,H,W,3) or float (n,3,H,W); intrinsics (n,3,3) normalised (or pixels with pixel_intrinsics), extrinsics (n,4,4) c2w
+      styles   one style image or a sequence of them, uint8 (Hs,Ws,3) or float (3,Hs,Ws); their sizes may differ, each comes out
+               cfg.style_size x cfg.style_size
+    Everything is returned on `device` (default: where the frames are)."""
+    cfg = cfg or InputCfg()
+    style_list = [styles] if isinstance(styles, Tensor) else list(styles)
+    ex = prepare_example(frames, intrinsics, extrinsics, context_indices, target_indices, None, cfg, stage="test",
+                         pixel_intrinsics=pixel_intrinsics, flip=False, scene=scene, device=device)
+    dev = ex["context"]["image"].device
+    batch = lambda views: {k: v[None] for k, v in views.items()}
+    return batch(ex["context"]), [apply_style_image_augmentation(s.to(dev), "test", cfg.style_size) for s in style_list], batch(ex["target"])
 
 
 def stylize_scene(encoder, decoder, context: dict, styles, target: dict, *, align: Optional[TestCfg] = None,
