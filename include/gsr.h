@@ -454,6 +454,26 @@ int gsr_resample_crop(const void *src, int src_is_f32, int64_t N, int H, int W, 
                       float *out, int flags, void *stream);
 
 /*
+ * View selection (csrc/gsr_views.hip): the mutual overlap of view pairs, as the reference's evaluation-index generator computes it
+ * (src/evaluation/evaluation_index_generator.py: get_world_rays of sample_image_grid, then src/geometry/epipolar_lines.py::project_rays
+ * with near = far = None, epsilon 1e-6).  counts[p][0] is the number of the H * W pixel rays of view pairs[p][0] whose projected
+ * segment overlaps the image of view pairs[p][1]; counts[p][1] is the same with the two views swapped.  float32(count) / float32(H * W)
+ * is the reference's overlaps_image.float().mean() bit for bit.
+ *     extrinsics (V,4,4) camera-to-world and intrinsics (V,3,3) normalised, fp32 on the device, widened to float64; both inverses
+ *     (3 x 3, general 4 x 4) are formed on the device in float64 by a prologue launch that also re-arms the counters.  Pixel
+ *     coordinates are (idx + 0.5) / length in fp32, widened; everything after them is float64 without contraction.
+ *     pairs (P,2) int32 and counts (P,2) int32 on the device.  A pair that names a view outside [0, V) gets -1 in both slots and no
+ *     camera is read for it.  Singular cameras give what IEEE arithmetic gives.
+ *     scratch: the scratch_bytes query's size in device memory (8-byte aligned, uninitialised; the query answers 0 for invalid V / P).
+ *     Two launches, no host sync, integer atomics only: two runs give the same counts.
+ * GSR_EINVAL before any launch: null pointers, V < 1, P < 1 or > 2^22, H or W < 1, H * W > 2^24 (the bound that keeps the fp32 mean
+ * exact); GSR_ENOSPACE: scratch too small.
+ */
+size_t gsr_view_overlap_scratch_bytes(int V, int64_t P);
+int gsr_view_overlap(const float *extrinsics, const float *intrinsics, int V, const int32_t *pairs, int64_t P, int H, int W, void *scratch,
+                     size_t scratch_bytes, int32_t *counts, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

@@ -18,7 +18,7 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip"]
 _HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
@@ -128,7 +128,8 @@ EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_f
            "gsr_pointmap_post", "gsr_regr3d_scratch_bytes", "gsr_regr3d_fwd", "gsr_regr3d_bwd",
            "gsr_k6_blocks_per_cu", "gsr_test_reduce9",
            "gsr_trajectory", "gsr_outputs_scratch_bytes", "gsr_depth_range", "gsr_pack_frames", "gsr_ply_normalizer", "gsr_ply_rows",
-           "gsr_resample_plan", "gsr_resample_scratch_bytes", "gsr_resample_crop")
+           "gsr_resample_plan", "gsr_resample_scratch_bytes", "gsr_resample_crop",
+           "gsr_view_overlap_scratch_bytes", "gsr_view_overlap")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -223,6 +224,10 @@ def load() -> C.CDLL:
     lib.gsr_resample_crop.argtypes = [vp, C.c_int, i64, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, sz, vp,
                                       C.c_int, vp]
     lib.gsr_resample_crop.restype = C.c_int
+    lib.gsr_view_overlap_scratch_bytes.argtypes = [C.c_int, i64]
+    lib.gsr_view_overlap_scratch_bytes.restype = C.c_size_t
+    lib.gsr_view_overlap.argtypes = [vp, vp, C.c_int, vp, i64, C.c_int, C.c_int, vp, sz, vp, vp]
+    lib.gsr_view_overlap.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

@@ -17,7 +17,8 @@ The rules (PIL's 8-bit resize, restated):
   float      float32(double(byte) / 255)
   flip       at the source read, before the filter (the reference reflects before it rescales; plans and crop offsets are not symmetric)
 
-Reading `.torch` chunks, decoding JPEGs, undistortion, the view samplers and the COLMAP parsers stay with the caller.
+Reading `.torch` chunks, decoding JPEGs, undistortion and the COLMAP parsers stay with the caller; the view samplers are in
+styl3r_amd/views.py and `example_from_scene` runs one in front of `prepare_example`.
 """
 from __future__ import annotations
 
@@ -418,6 +419,19 @@ def prepare_example(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, cont
     if style is not None:
         example["style"] = {"image": apply_style_image_augmentation(_to_device(style, device), stage, cfg.style_size)}
     return example
+
+
+def example_from_scene(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, sampler, scene: str, style, cfg: InputCfg, *, stage: str,
+                       **kwargs) -> dict:
+    """`prepare_example` with the views chosen by a view sampler (styl3r_amd.views): sampler.sample(scene, extrinsics, intrinsics) gives
+    the context and target indices.  A scene the sampler refuses (ValueError: "Example does not have enough frames!", no entry in the
+    evaluation index) raises SkipExample, where the reference's loader `continue`s (dataset_re10k_style.py:125-133).  kwargs go to
+    prepare_example."""
+    try:
+        picked = sampler.sample(scene, extrinsics, intrinsics)
+    except ValueError as err:
+        raise SkipExample(str(err)) from err
+    return prepare_example(frames, intrinsics, extrinsics, picked[0], picked[1], style, cfg, stage=stage, scene=scene, **kwargs)
 
 
 def collate(examples: Sequence[dict]) -> dict:
