@@ -474,6 +474,32 @@ int gsr_view_overlap(const float *extrinsics, const float *intrinsics, int V, co
                      size_t scratch_bytes, int32_t *counts, void *stream);
 
 /*
+ * gsr_draw_layers (validation visuals; the reference's src/visualization/drawing/): anti-aliased lines and points drawn over B planar
+ * fp32 images (B,3,H,W) on the device, `out` = `images` for in-place.  Image b carries the ordered layers image_layers[b] ..
+ * image_layers[b + 1] - 1 (int32 (B + 1,)); layer l carries the records layer_prims[l] .. layer_prims[l + 1] - 1 (int32 (NL + 1,)) and is
+ * drawn with layer_msaa[l] in {0, 1} MSAA passes: one layer is one render_over_image(subdivision = 8) of the reference -- centre sample
+ * per pixel, top primitive = highest covering index, RGBA (colour[top], 1) or (colour[first], 0); a pixel that differs from any of its
+ * 8 neighbours inside the image is re-sampled at 8 x 8 offsets, colour = sum(c a) / (sum(a) + 1e-10), alpha = mean(a); then
+ * image (1 - alpha) + colour alpha.  Layers composite in order in float64, the pixel is rounded to fp32 once.  An empty layer draws nothing.
+ *     prims (NP, GSR_DRAW_RECORD_DOUBLES) float64 on the device, 16-byte aligned, pixel space:
+ *       [0] kind GSR_DRAW_*   [1] colour class: lowest index WITHIN the layer of a primitive with the same colour
+ *       line : [2,3] start  [4,5] end  [6,7] (end - start) / |end - start| (NaN when degenerate)  [8] |end - start| + extra
+ *              [9] -extra  [10] width / 2  [11..13] RGB, with extra = width / 2 for square caps and 0 otherwise
+ *       point: [2,3] centre  [8] inner radius  [10] radius  [11..13] RGB
+ *     The tables are the caller's: indices outside [0, NL] / [0, NP] are clamped, never followed.  Colours must be finite.
+ *     One launch, no atomics, no host sync: two runs give the same bits.  O(pixels x primitives), no primitive cap.
+ * GSR_EINVAL before the launch: null pointers, B < 1 or > 65535, H or W < 1, H * W > 2^28, NP > 2^30, prims not 16-byte aligned.
+ */
+#define GSR_DRAW_RECORD_DOUBLES 16
+#define GSR_DRAW_CHUNK 32 /* records staged through LDS at a time */
+#define GSR_DRAW_BUTT 0
+#define GSR_DRAW_ROUND 1
+#define GSR_DRAW_SQUARE 2
+#define GSR_DRAW_POINT 3
+int gsr_draw_layers(const float *images, float *out, int B, int H, int W, const int32_t *image_layers, const int32_t *layer_prims,
+                    const int32_t *layer_msaa, int NL, const double *prims, int64_t NP, void *stream);
+
+/*
  * Optional per-stage timing with hipEvents recorded on the caller's stream
  * between the kernels of gsr_forward / gsr_backward (bench.py's live roofline
  * measurement).  A profile holds event pairs for `max_calls` forward and

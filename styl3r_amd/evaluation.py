@@ -109,6 +109,42 @@ def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = Te
 test_step.__test__ = False                       # (not a pytest test function where a test module imports it)
 
 
+def validation_step(encoder, decoder, batch: dict, step: int = 0, labeler=None, lpips: Optional[LPIPS] = None, style: Optional[dict] = None,
+                    extra_columns: Sequence = (), resolution: int = 256):
+    """validation_step (:472-617) for the first scene of `batch` (the reference asserts b == 1): encoder and decoder as `test_step` runs them, the
+    three scores as `val/psnr`, `val/ssim`, `val/lpips` (means over the target views) and the three pictures of
+    `visualization.validation_images`.  The style is `style` if given, else `batch["style"]` as the reference takes it -- its image rescaled to
+    [-1, 1] for an encoder with `stylized` set, and shown unscaled as the Style panel -- else the first context image, without a Style panel
+    (the reference needs `batch["style"]`).  Images of the batch are in [0, 1], as everywhere in this package (the reference un-normalises its
+    context images here).  The context depth is the dump's depth; more than one value per pixel is averaged (the reference averages exactly
+    three and shows one as it is).  Returns (DecoderOutput, scores, images); logging, the videos and the encoder visualizer stay with the caller."""
+    from .visualization import validation_images
+    ctx, tgt = batch["context"], batch["target"]
+    _, v, _, h, w = tgt["image"].shape
+    style_panel = None
+    if style is None and "style" in batch:
+        style = dict(batch["style"])
+        style_panel = style["image"][0]
+        if getattr(encoder, "stylized", False):
+            style["image"] = (style["image"] - 0.5) / 0.5
+    elif style is None:
+        style = {"image": ctx["image"][:, 0]}
+    dump = {}
+    with torch.no_grad():
+        gaussians = encoder(ctx, style, step, visualization_dump=dump)
+        output = decoder.forward(gaussians, tgt["extrinsics"], tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
+    gt, pred = tgt["image"][0], output.color[0]
+    module = lpips if lpips is not None else metrics.get_lpips(pred.device)
+    psnr, ssim = metrics.image_scores(gt, pred)
+    scores = {"val/psnr": psnr.mean(), "val/ssim": ssim.mean(), "val/lpips": metrics.compute_lpips(gt, pred, module).mean(),
+              "lpips_weights_loaded": bool(getattr(module, "weights_loaded", False))}
+    context_depth = dump["depth"][0].reshape(ctx["image"].shape[1], *ctx["image"].shape[-2:], -1)
+    context_depth = context_depth[..., 0] if context_depth.shape[-1] == 1 else context_depth.mean(dim=-1)
+    images = validation_images(ctx["image"][0], context_depth, gt, pred, output.depth[0], gaussians, batch, extra_columns=extra_columns,
+                               style_image=style_panel, labeler=labeler, resolution=resolution)
+    return output, scores, images
+
+
 # ---- relative pose between the context views (src/evaluation/pose_evaluator.py:48-164) ------------------------------------------------
 @dataclass
 class PoseEvalCfg:
