@@ -474,6 +474,30 @@ int gsr_view_overlap(const float *extrinsics, const float *intrinsics, int V, co
                      size_t scratch_bytes, int32_t *counts, void *stream);
 
 /*
+ * Lens undistortion of 8-bit frames (csrc/gsr_undistort.hip; the reference's COLMAP drivers: initUndistortRectifyMap + remap with
+ * INTER_LINEAR and a zero border + the crop to the valid-pixel ROI, per image on the host).  src (N,H,W,3) and dst (N,roi_h,roi_w,3)
+ * are interleaved bytes on the device, dst 4-byte aligned.  Frame n belongs to camera frame_cam[n]; frame_cam is an int32 (N) array
+ * on the HOST: it is checked here and handed to the kernel in its argument block.  cams is a device table of n_cams rows of
+ * GSR_UNDISTORT_CAM_DOUBLES float64, 8-byte aligned:
+ *       [0..3] fx fy cx cy of the distorted camera   [4..7] k1 k2 p1 p2   [8..11] fx' fy' cx' cy' of the undistorted camera
+ *       [12,13] x, y of the ROI origin in the full undistorted frame (integers)   [14] 0: no distortion, the frame is copied through its
+ *       window; otherwise remap   [15] reserved, 0
+ * Output pixel (u, v) is pixel (u + x, v + y) of the full W x H undistorted frame.  Its source coordinate is evaluated in float64
+ * without contraction -- x = (u - cx') / fx', y = (v - cy') / fy', r2 = x x + y y, kr = 1 + (k2 r2 + k1) r2,
+ * xd = x kr + p1 (2 x y) + p2 (r2 + 2 x x), yd = y kr + p1 (r2 + 2 y y) + p2 (2 x y), mx = float32(fx xd + cx), my = float32(fy yd + cy)
+ * -- and sampled in 1/32-pixel fixed point: sx = rint(mx * 32) half to even, ix = sx >> 5, a = sx & 31 (iy, b likewise),
+ * byte = ((32 - a)(32 - b) p00 + a (32 - b) p01 + (32 - a) b p10 + a b p11 + 512) >> 10 with 0 for a tap outside the image; a non-finite
+ * coordinate or one with |m| * 32 >= 2^30 gives 0.  The table's values are the caller's: every source read is bounds-checked whatever
+ * they are.  One launch per GSR_UNDISTORT_FRAMES_PER_LAUNCH frames, no map arrays, no scratch, no atomics, no host sync.
+ * GSR_EINVAL before any launch: null pointers, misaligned cams / dst, N < 1 or > 2^24, H or W < 1 or > 32767, n_cams < 1 or > 65535,
+ * a frame_cam entry outside [0, n_cams), roi_w or roi_h < 1 (an empty ROI) or > 32767.
+ */
+#define GSR_UNDISTORT_CAM_DOUBLES 16
+#define GSR_UNDISTORT_FRAMES_PER_LAUNCH 1024
+int gsr_undistort(const uint8_t *src, int64_t N, int H, int W, const double *cams, int n_cams, const int32_t *frame_cam, int roi_w,
+                  int roi_h, uint8_t *dst, void *stream);
+
+/*
  * gsr_draw_layers (validation visuals; the reference's src/visualization/drawing/): anti-aliased lines and points drawn over B planar
  * fp32 images (B,3,H,W) on the device, `out` = `images` for in-place.  Image b carries the ordered layers image_layers[b] ..
  * image_layers[b + 1] - 1 (int32 (B + 1,)); layer l carries the records layer_prims[l] .. layer_prims[l + 1] - 1 (int32 (NL + 1,)) and is

@@ -18,7 +18,7 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip"]
 _HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
@@ -121,6 +121,7 @@ GSR_N_STAGES = 7
 GSR_PT_EMPTY_MAP, GSR_PT_NAN, GSR_PT_EMPTY_VIEW = 1, 2, 4     # status bits of gsr_regr3d_fwd
 GSR_DRAW_RECORD_DOUBLES, GSR_DRAW_CHUNK = 16, 32                    # gsr_draw_layers: doubles per record, records per LDS chunk
 GSR_DRAW_BUTT, GSR_DRAW_ROUND, GSR_DRAW_SQUARE, GSR_DRAW_POINT = 0, 1, 2, 3
+GSR_UNDISTORT_CAM_DOUBLES, GSR_UNDISTORT_FRAMES_PER_LAUNCH = 16, 1024     # gsr_undistort: doubles per camera row, frames per launch
 GSR_DEPTH_NO_POSITIVE = 1                                     # status[1] of gsr_depth_range
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_fused", "gsr_backward_fused", "gsr_version", "gsr_profile_create",
@@ -131,7 +132,7 @@ EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_f
            "gsr_k6_blocks_per_cu", "gsr_test_reduce9",
            "gsr_trajectory", "gsr_outputs_scratch_bytes", "gsr_depth_range", "gsr_pack_frames", "gsr_ply_normalizer", "gsr_ply_rows",
            "gsr_resample_plan", "gsr_resample_scratch_bytes", "gsr_resample_crop",
-           "gsr_view_overlap_scratch_bytes", "gsr_view_overlap", "gsr_draw_layers")
+           "gsr_view_overlap_scratch_bytes", "gsr_view_overlap", "gsr_draw_layers", "gsr_undistort")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -232,6 +233,8 @@ def load() -> C.CDLL:
     lib.gsr_view_overlap.restype = C.c_int
     lib.gsr_draw_layers.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, i64, vp]
     lib.gsr_draw_layers.restype = C.c_int
+    lib.gsr_undistort.argtypes = [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
+    lib.gsr_undistort.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

@@ -6,7 +6,8 @@ poses on the un-stylized Gaussians, then renders the plain and every stylized se
 (set, camera list).  Here the style-independent part of the encoder runs once (`encode_scene`), all styles of one image size go
 through ONE `restyle` batch, and the plain + S stylized sets -- which share means, covariances and opacities -- are rendered by ONE
 `forward_styles` call.  `prepare_scene` is the other end: decoded frames and raw cameras in, the (context, styles, target) that
-`stylize_scene` takes out, images rescaled and cropped on the device (inputs.py).  `render_flythrough` turns the result into the frames of the drivers' videos (render_video_generic and the
+`stylize_scene` takes out, images rescaled and cropped on the device (inputs.py); `prepare_colmap_scene` is the same end for a COLMAP
+capture loaded by `colmap.load_colmap_scene` (infer_model_colmap.py), its frames undistorted on the device first.  `render_flythrough` turns the result into the frames of the drivers' videos (render_video_generic and the
 wrapper's three trajectories) and `export_scene_ply` into their .ply files; encoding a container, decoding the frames and the
 dataset readers stay with the caller.
 
@@ -29,6 +30,7 @@ from .evaluation import TestCfg, align_target_poses
 from .export import depth_range, export_ply, pack_frames
 from .inputs import InputCfg, apply_style_image_augmentation, prepare_example
 from .trajectory import KINDS, trajectory_cameras
+from . import colmap
 
 
 @dataclass
@@ -64,6 +66,34 @@ def prepare_scene(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, contex
     dev = ex["context"]["image"].device
     batch = lambda views: {k: v[None] for k, v in views.items()}
     return batch(ex["context"]), [apply_style_image_augmentation(s.to(dev), "test", cfg.style_size) for s in style_list], batch(ex["target"])
+
+
+def prepare_colmap_scene(scene: "colmap.ColmapScene", ctx_indices, num_ctx_views: int, styles, cfg: Optional[InputCfg] = None, *,
+                         frames: Optional[Tensor] = None, device=None):
+    """A loaded COLMAP scene -> (context, styles, target) as `stylize_scene` takes them, following infer_model_colmap.py:480-589:
+    `colmap.select_colmap_views`, the selected frames read from `scene.image_paths` (or taken from `frames`, uint8 (n,H,W,3) over ALL
+    images of the scene in its order), uploaded as bytes, undistorted in one `colmap.undistort_frames` call, pixel intrinsics per image
+    from `scene.Ks`, then `prepare_scene(..., pixel_intrinsics=True)`: baseline-1 rescale, relative poses, near / far, rescale and crop.
+    The ROI origin of each camera is subtracted from cx, cy (the reference crops to the ROI without moving the principal point, which
+    is harmless only for an origin of (0, 0)).  "index" holds the scene's image indices."""
+    import numpy as np
+    context_idx, target_idx = colmap.select_colmap_views(ctx_indices, num_ctx_views)
+    sel = torch.cat([context_idx, target_idx])
+    picked = colmap.read_frames([scene.image_paths[i] for i in sel.tolist()]) if frames is None else frames.index_select(0, sel.to(frames.device))
+    if device is not None:
+        picked = picked.to(device)
+    cam_ids = [scene.camera_ids[i] for i in sel.tolist()]
+    undistorted = colmap.undistort_frames(picked, scene, cam_ids)
+    K = np.stack([scene.Ks[c] for c in cam_ids]).astype(np.float64)
+    K[:, 0, 2] -= np.array([scene.rois[c][0] for c in cam_ids], dtype=np.float64)
+    K[:, 1, 2] -= np.array([scene.rois[c][1] for c in cam_ids], dtype=np.float64)
+    E = np.asarray(scene.camtoworlds, dtype=np.float64)[sel.numpy()]
+    n_ctx = context_idx.shape[0]
+    context, style_list, target = prepare_scene(undistorted, torch.from_numpy(K), torch.from_numpy(E), range(n_ctx), range(n_ctx, sel.shape[0]),
+                                                styles, cfg, pixel_intrinsics=True, scene=scene.name, device=device)
+    dev = context["image"].device
+    context["index"], target["index"] = context_idx.to(dev)[None], target_idx.to(dev)[None]
+    return context, style_list, target
 
 
 def stylize_scene(encoder, decoder, context: dict, styles, target: dict, *, align: Optional[TestCfg] = None,
