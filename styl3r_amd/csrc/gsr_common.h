@@ -121,6 +121,19 @@ int forward_styles(const GsrDims &d, int S, const GsrView *views, const float *m
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+// hands out 256-byte aligned arrays of a scratch buffer in order; with a null base it only counts (`off`: the bytes taken so far)
+struct Carver {
+    void *base;
+    size_t off;
+    template <class T>
+    T *take(size_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(static_cast<char *>(base) + off) : nullptr;
+        off += align_up(count * sizeof(T), 256);
+        return p;
+    }
+};
+
 // f(std::integral_constant<int, DEG>) with DEG the compile-time form of the launch's SH degree: 0..4, or -1 for precomputed colours (M = 0)
 template <class F>
 inline void with_sh_degree(const GsrDims &d, F &&f)

@@ -11,10 +11,10 @@
 //   gsr_ply_normalizer : (median xyz, factor) of export_ply(shift_and_scale=True), two selections.
 //   gsr_ply_rows       : the packed fp32 vertex table; the quaternion goes through scipy's quat -> matrix -> quat round trip in float64.
 //
-// Selection here: keys are the order-preserving image of the fp32 bits (negative values included), a map is cut into chunks over many
-// workgroups that add LDS histograms into a global integer histogram, and one workgroup per map picks the digits between the passes
-// (eight launches).  Two rank pairs ("groups") are followed together; a group counts its own subset (all / the positive depths), and
-// its ranks come from the subset's count, which pass 0 leaves behind.  No host sync, no float atomics, two runs give the same bits.
+// Selection: the engine is gsr_select.h.  This file supplies the source OSel -- a depth, a coordinate or |coordinate - median| as the
+// value, the plan of each use (depth range: q 0.99 of all depths and q 0.01 of the positive ones; normaliser: the lower median, then
+// q 0.95, per axis), no finish hook -- the chunk rule osel_chunks and the one-thread k_*_finish kernels that turn the selected values
+// into the outputs.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -31,16 +31,9 @@ namespace gsr {
 
 constexpr int OUT_BLOCK = 256, OSEL_MAX_MAPS = 3, OSEL_MAX_CHUNKS = 1024;
 enum { OSEL_DEPTH = 0, OSEL_AXIS = 1, OSEL_ABSDEV = 2 };
-constexpr float OSEL_MEDIAN = -1.0f;      // a group's q: the lower median instead of a quantile
 
-// per-map selection state, uint32 words
 struct OSelScratch {
-    uint32_t *hist;      // [maps][SEL_RANKS][SEL_BINS]
-    uint32_t *nanflag;   // [maps]
-    uint32_t *sel;       // [maps][SEL_RANKS][2]: key prefix found so far, rank left inside it
-    uint32_t *cnt;       // [maps][2]: elements counted by each group
-    float *w;            // [maps][2]: lerp weight of each group
-    float *vals;         // [maps][SEL_RANKS]: the selected values
+    SelScratch sel;      // OSEL_MAX_MAPS maps
     float *aux;          // [OSEL_MAX_MAPS]: the medians the second selection of the normaliser subtracts
     size_t total;
 };
@@ -48,16 +41,10 @@ struct OSelScratch {
 static OSelScratch osel_carve(void *base)
 {
     OSelScratch s;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { void *p = base ? static_cast<char *>(base) + off : nullptr; off += align_up(bytes, 256); return p; };
-    s.hist = static_cast<uint32_t *>(take((size_t)OSEL_MAX_MAPS * SEL_RANKS * SEL_BINS * 4));
-    s.nanflag = static_cast<uint32_t *>(take(OSEL_MAX_MAPS * 4));
-    s.sel = static_cast<uint32_t *>(take(OSEL_MAX_MAPS * SEL_RANKS * 2 * 4));
-    s.cnt = static_cast<uint32_t *>(take(OSEL_MAX_MAPS * 2 * 4));
-    s.w = static_cast<float *>(take(OSEL_MAX_MAPS * 2 * 4));
-    s.vals = static_cast<float *>(take(OSEL_MAX_MAPS * SEL_RANKS * 4));
-    s.aux = static_cast<float *>(take(OSEL_MAX_MAPS * 4));
-    s.total = off;
+    Carver c{base, 0};
+    s.sel = sel_carve(c, OSEL_MAX_MAPS);
+    s.aux = c.take<float>(OSEL_MAX_MAPS);
+    s.total = c.off;
     return s;
 }
 
@@ -66,115 +53,21 @@ struct OSel {
     const float *aux;    // ABSDEV: [3] medians
     long long n;
     int mode;
-    float q0, q1;        // group 0 / group 1 (q1 < -1.5: group 1 is not used)
+    float q0, q1;        // pair 0 over all elements, pair 1 over the positive ones (SEL_MEDIAN / SEL_UNUSED: gsr_select.h)
+    __device__ SelPlan plan() const { return {{q0, q1}, {SEL_ALL, SEL_POSITIVE}}; }      // (subsets as constants: the kernels fold them)
+    __device__ float value(int m, long long i, int) const
+    {
+        if (mode == OSEL_DEPTH) return x[i];
+        const float v = x[3 * i + m];
+        return mode == OSEL_AXIS ? v : fabsf(v - aux[m]);
+    }
+    __device__ void finish(int, const float *, const float *, bool) const {}      // (the k_*_finish kernels below read the scratch)
 };
-
-__device__ inline float osel_value(const OSel &s, int m, long long i)
-{
-    if (s.mode == OSEL_DEPTH) return s.x[i];
-    const float v = s.x[3 * i + m];
-    return s.mode == OSEL_AXIS ? v : fabsf(v - s.aux[m]);
-}
-// order-preserving: a < b as floats <=> key(a) < key(b) as unsigned (a NaN sorts at an end; the map's flag overrides the result)
-__device__ inline uint32_t osel_key(float v)
-{
-    const uint32_t u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ inline float osel_unkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
-
-// one digit pass over (chunk, map) workgroups.  Pass 0 counts the top byte per GROUP (rows 0, 1), the later passes the next byte of
-// the keys under each RANK's prefix (rows 0..3).
-__global__ void __launch_bounds__(OUT_BLOCK) k_osel_hist(OSel s, int pass, uint32_t *__restrict__ hist, const uint32_t *__restrict__ sel,
-                                                         uint32_t *__restrict__ nanflag)
-{
-    __shared__ uint32_t h[SEL_RANKS * SEL_BINS];
-    const int m = blockIdx.y, tid = threadIdx.x;
-    const long long per = (s.n + gridDim.x - 1) / gridDim.x, i0 = (long long)blockIdx.x * per, i1 = min(s.n, i0 + per);
-    const int rows = pass == 0 ? 2 : SEL_RANKS;
-    const bool two = s.q1 >= -1.5f;
-    for (int t = tid; t < rows * SEL_BINS; t += OUT_BLOCK) h[t] = 0u;
-    __syncthreads();
-    if (pass == 0) {
-        bool nan = false;
-        for (long long base = i0; base < i1; base += OUT_BLOCK) {       // (uniform trip count: the grouped bump is a wave-wide operation)
-            const long long i = base + tid;
-            const bool ok = i < i1;
-            float v = 0.f;
-            if (ok) { v = osel_value(s, m, i); nan |= v != v; }
-            const uint32_t dg = osel_key(v) >> 24;
-            hist_bump_grouped(h, dg, ok);
-            if (two) hist_bump_grouped(h + SEL_BINS, dg, ok && v > 0.f);
-        }
-        if (nan) atomicOr(nanflag + m, 1u);
-    } else {
-        const int shift = 24 - 8 * pass;
-        const uint32_t *sp = sel + (size_t)m * SEL_RANKS * 2;
-        const uint32_t p0 = sp[0] >> (shift + 8), p1 = sp[2] >> (shift + 8), p2 = sp[4] >> (shift + 8), p3 = sp[6] >> (shift + 8);
-        for (long long i = i0 + tid; i < i1; i += OUT_BLOCK) {
-            const float v = osel_value(s, m, i);
-            const uint32_t key = osel_key(v), top = key >> (shift + 8), dg = (key >> shift) & 255u;
-            if (top == p0) atomicAdd(h + dg, 1u);
-            if (top == p1) atomicAdd(h + SEL_BINS + dg, 1u);
-            if (two && v > 0.f) {
-                if (top == p2) atomicAdd(h + 2 * SEL_BINS + dg, 1u);
-                if (top == p3) atomicAdd(h + 3 * SEL_BINS + dg, 1u);
-            }
-        }
-    }
-    __syncthreads();
-    uint32_t *hg = hist + (size_t)m * SEL_RANKS * SEL_BINS;
-    for (int t = tid; t < rows * SEL_BINS; t += OUT_BLOCK)
-        if (h[t]) atomicAdd(hg + t, h[t]);
-}
-
-// one workgroup per map, wave r follows rank r (group r / 2).  Pass 0 also turns the group's count into its two ranks.
-__global__ void __launch_bounds__(OUT_BLOCK) k_osel_pick(float q0, float q1, int pass, uint32_t *__restrict__ hist, uint32_t *__restrict__ sel,
-                                                         uint32_t *__restrict__ cnt, float *__restrict__ w, float *__restrict__ vals)
-{
-    const int m = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, grp = wave >> 1, shift = 24 - 8 * pass;
-    uint32_t *hg = hist + (size_t)m * SEL_RANKS * SEL_BINS, *sp = sel + (size_t)m * SEL_RANKS * 2;
-    uint32_t k, before = 0u;
-    if (pass == 0) {
-        const uint32_t *row = hg + grp * SEL_BINS;
-        uint32_t c = row[4 * lane] + row[4 * lane + 1] + row[4 * lane + 2] + row[4 * lane + 3];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) c += (uint32_t)__shfl_xor((int)c, o, 64);
-        const float q = grp ? q1 : q0;
-        uint32_t kk[2] = {0u, 0u};
-        float wt = 0.f;
-        if (c > 0u && q >= 0.f) sel_rank_pair(q, (long long)c, kk, &wt);
-        else if (c > 0u && q >= -1.5f) kk[0] = kk[1] = (c - 1u) >> 1;             // torch.median: the lower of the two middle elements
-        k = (wave & 1) ? kk[1] : kk[0];
-        if (lane == 0 && !(wave & 1)) { cnt[2 * m + grp] = c; w[2 * m + grp] = wt; }
-    } else {
-        k = sp[2 * wave + 1];
-        before = sp[2 * wave];
-    }
-    const uint32_t d = sel_pick(hg + (pass == 0 ? grp : wave) * SEL_BINS, k);
-    const uint32_t now = before | (d << shift);
-    if (lane == 0) {
-        sp[2 * wave] = now; sp[2 * wave + 1] = k;
-        if (pass == SEL_PASSES - 1) vals[SEL_RANKS * m + wave] = osel_unkey(now);
-    }
-    __syncthreads();
-    for (int t = tid; t < SEL_RANKS * SEL_BINS; t += OUT_BLOCK) hg[t] = 0u;      // re-armed for the next pass (and the next selection)
-}
 
 static int osel_chunks(long long n)
 {
     long long c = (n + 4095) / 4096;
     return (int)(c < 1 ? 1 : (c > OSEL_MAX_CHUNKS ? OSEL_MAX_CHUNKS : c));
-}
-
-// the eight launches of one selection over `maps` maps; histograms and NaN flags must be zero on entry (the picks leave the histograms so)
-static void osel_run(const OSel &s, int maps, const OSelScratch &sc, hipStream_t st)
-{
-    const int chunks = osel_chunks(s.n);
-    for (int pass = 0; pass < SEL_PASSES; ++pass) {
-        hipLaunchKernelGGL(k_osel_hist, dim3(chunks, maps), dim3(OUT_BLOCK), 0, st, s, pass, sc.hist, sc.sel, sc.nanflag);
-        hipLaunchKernelGGL(k_osel_pick, dim3(maps), dim3(OUT_BLOCK), 0, st, s.q0, s.q1, pass, sc.hist, sc.sel, sc.cnt, sc.w, sc.vals);
-    }
 }
 
 // ---- depth range ----
@@ -571,10 +464,11 @@ __attribute__((visibility("default"))) int gsr_depth_range(const float *depth, i
     if (ne > (1LL << 31)) return GSR_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const OSelScratch sc = osel_carve(scratch);
-    if (!hip_ok(hipMemsetAsync(sc.hist, 0, reinterpret_cast<char *>(sc.sel) - reinterpret_cast<char *>(sc.hist), s))) return GSR_ELAUNCH;
+    const SelScratch &ss = sc.sel;
+    if (!hip_ok(hipMemsetAsync(ss.hist, 0, sel_zero_bytes(ss), s))) return GSR_ELAUNCH;
     (void)hipGetLastError();
-    osel_run(OSel{depth, nullptr, ne, OSEL_DEPTH, 0.99f, 0.01f}, 1, sc, s);
-    hipLaunchKernelGGL(k_depth_range_finish, dim3(1), dim3(64), 0, s, sc.nanflag, sc.cnt, sc.w, sc.vals, range, status);
+    sel_run(OSel{depth, nullptr, ne, OSEL_DEPTH, 0.99f, 0.01f}, 1, osel_chunks(ne), ss, s);
+    hipLaunchKernelGGL(k_depth_range_finish, dim3(1), dim3(64), 0, s, ss.nanflag, ss.cnt, ss.w, ss.vals, range, status);
     return launch_status();
 }
 
@@ -614,13 +508,15 @@ __attribute__((visibility("default"))) int gsr_ply_normalizer(const float *means
     if (!means || !scratch || !out || G < 2 || G > (1LL << 31)) return GSR_EINVAL;
     hipStream_t s = static_cast<hipStream_t>(stream);
     const OSelScratch sc = osel_carve(scratch);
-    if (!hip_ok(hipMemsetAsync(sc.hist, 0, reinterpret_cast<char *>(sc.sel) - reinterpret_cast<char *>(sc.hist), s))) return GSR_ELAUNCH;
+    const SelScratch &ss = sc.sel;
+    const int chunks = osel_chunks(G);
+    if (!hip_ok(hipMemsetAsync(ss.hist, 0, sel_zero_bytes(ss), s))) return GSR_ELAUNCH;
     (void)hipGetLastError();
-    osel_run(OSel{means, nullptr, (long long)G, OSEL_AXIS, OSEL_MEDIAN, -2.f}, 3, sc, s);
-    hipLaunchKernelGGL(k_ply_median_finish, dim3(1), dim3(64), 0, s, sc.nanflag, sc.vals, sc.aux, out);
+    sel_run(OSel{means, nullptr, (long long)G, OSEL_AXIS, SEL_MEDIAN, SEL_UNUSED}, 3, chunks, ss, s);
+    hipLaunchKernelGGL(k_ply_median_finish, dim3(1), dim3(64), 0, s, ss.nanflag, ss.vals, sc.aux, out);
     // (the picks left the histograms at zero; a NaN flag stays up: |x - median| of that axis holds the NaN again)
-    osel_run(OSel{means, sc.aux, (long long)G, OSEL_ABSDEV, 0.95f, -2.f}, 3, sc, s);
-    hipLaunchKernelGGL(k_ply_factor_finish, dim3(1), dim3(64), 0, s, sc.nanflag, sc.w, sc.vals, out);
+    sel_run(OSel{means, sc.aux, (long long)G, OSEL_ABSDEV, 0.95f, SEL_UNUSED}, 3, chunks, ss, s);
+    hipLaunchKernelGGL(k_ply_factor_finish, dim3(1), dim3(64), 0, s, ss.nanflag, ss.w, ss.vals, out);
     return launch_status();
 }
 

@@ -2,17 +2,19 @@
 //
 //   gsr_pointmap_post : the teacher head's post-processing (heads/postprocess.py, depth mode ('exp', -inf, inf), conf mode ('exp', 1, inf))
 //                       in one pass over the (P,4,H,W) head output.
-//   gsr_regr3d_fwd    : Regr3D.  Per (view, image) map the 0.2 % / 99.8 % quantiles of |gt| by RADIX SELECTION on the fp32 bit pattern
-//                       (monotone for non-negative values) -- four 8-bit digit passes, LDS histograms bumped with integer atomics, the four
-//                       ranks floor / ceil of both quantile positions followed together -- instead of torch.quantile's two full row sorts;
-//                       then the valid mask, the joint avg_dis normalisation and the masked Euclidean distance, reduced through
-//                       per-workgroup float64 partials that ONE thread per map folds in index order (two runs are bit-identical).
+//   gsr_regr3d_fwd    : Regr3D.  Per (view, image) map the 0.2 % / 99.8 % quantiles of |gt| by the exact radix selection of
+//                       gsr_select.h -- the four ranks floor / ceil of both quantile positions followed together -- instead of
+//                       torch.quantile's two full row sorts; then the valid mask, the joint avg_dis normalisation and the masked
+//                       Euclidean distance, reduced through per-workgroup float64 partials that ONE thread per map folds in index
+//                       order (two runs are bit-identical).
 //   gsr_regr3d_bwd    : one element-wise pass; the per-image reduction the avg_dis scale needs is left behind by the forward.
 //
-// Selection grids: maps of at most SEL_ONE_MAX_N points take ONE workgroup each (keys in registers, histogram and pick in LDS, one
-// launch); larger maps are cut into chunks over several workgroups that add their LDS histograms into a global integer histogram,
-// with a one-workgroup-per-map pick step between the digit passes (eight launches), so that two maps of 65 536 points still fill
-// the chip.  Nothing syncs with the host, there are no float atomics, and the launch sequence depends on (B, N, mode) only.
+// Selection: the engine (keys, histogram and pick kernels, ranks, scratch, launch loop) is gsr_select.h.  This file supplies the source
+// PtSel -- |gt| computed and stored to `dis` on pass 0 and read back afterwards, both quantiles over all points, the lerp with the NaN
+// override as the finish -- the chunk rule pt_chunks, and k_sel_one: maps of at most SEL_ONE_MAX_N points take ONE workgroup each
+// (keys in registers, histogram and pick in LDS, one launch instead of eight), built from the engine's key, bump, pick and ranks and
+// from PtSel's value and finish.  Nothing syncs with the host, there are no float atomics, and the launch sequence depends on
+// (B, N, mode) only.
 //
 // Deviation from the reference (deliberate): a view whose valid set is empty contributes 0 with a zero gradient (the reference
 // returns NaN, the mean of an empty tensor); `status` reports it.
@@ -37,9 +39,7 @@ constexpr float CONF_MIN = 3.0f;
 struct PtScratch {
     float *dis;          // [2B][N]   |gt|
     uint8_t *mask;       // [2B][N]   valid
-    uint32_t *hist;      // [2B][SEL_RANKS][SEL_BINS]
-    uint32_t *sel;       // [2B][SEL_RANKS][2]: key prefix found so far, rank left inside it
-    uint32_t *nanflag;   // [2B]
+    SelScratch sel;      // [2B] maps
     float *quant;        // [2B][2]
     double *part;        // [2B][PT_MAX_CHUNKS][4]: count, sum |pr|, sum |gt|, sum |pr - gt|
     double *part2;       // [2B][PT_MAX_CHUNKS][2]: sum |pr/s - gt/s'|, sum u . pr
@@ -52,21 +52,18 @@ struct PtScratch {
 static PtScratch pt_carve(void *base, int B, long long N)
 {
     PtScratch s;
-    size_t off = 0;
+    Carver c{base, 0};
     const size_t maps = 2 * (size_t)B;
-    auto take = [&](size_t bytes) { void *p = base ? static_cast<char *>(base) + off : nullptr; off += align_up(bytes, 256); return p; };
-    s.dis = static_cast<float *>(take(maps * N * 4));
-    s.mask = static_cast<uint8_t *>(take(maps * N));
-    s.hist = static_cast<uint32_t *>(take(maps * SEL_RANKS * SEL_BINS * 4));
-    s.sel = static_cast<uint32_t *>(take(maps * SEL_RANKS * 2 * 4));
-    s.nanflag = static_cast<uint32_t *>(take(maps * 4));
-    s.quant = static_cast<float *>(take(maps * 2 * 4));
-    s.part = static_cast<double *>(take(maps * PT_MAX_CHUNKS * 4 * 8));
-    s.part2 = static_cast<double *>(take(maps * PT_MAX_CHUNKS * 2 * 8));
-    s.mapsum = static_cast<double *>(take(maps * 6 * 8));
-    s.img = static_cast<double *>(take((size_t)B * 4 * 8));
-    s.glob = static_cast<double *>(take(2 * 8));
-    s.total = off;
+    s.dis = c.take<float>(maps * N);
+    s.mask = c.take<uint8_t>(maps * N);
+    s.sel = sel_carve(c, maps);
+    s.quant = c.take<float>(maps * 2);
+    s.part = c.take<double>(maps * PT_MAX_CHUNKS * 4);
+    s.part2 = c.take<double>(maps * PT_MAX_CHUNKS * 2);
+    s.mapsum = c.take<double>(maps * 6);
+    s.img = c.take<double>((size_t)B * 4);
+    s.glob = c.take<double>(2);
+    s.total = c.off;
     return s;
 }
 
@@ -83,52 +80,58 @@ __device__ inline float pt_dis(const float *__restrict__ p)
     const float x = p[0], y = p[1], z = p[2];
     return sqrtf(x * x + y * y + z * z);
 }
-__device__ inline uint32_t pt_key(float d) { return __float_as_uint(d) & 0x7fffffffu; }    // (a NaN sorts behind +inf; the map's flag overrides the result)
 
-// the four ranks torch.quantile reads for q = 0.002 and 0.998
-__device__ inline void sel_ranks(long long N, uint32_t *k, float *w)
-{
-    sel_rank_pair(0.002f, N, k, w);
-    sel_rank_pair(0.998f, N, k + 2, w + 1);
-}
-
-__device__ inline void sel_finish(const uint32_t *prefix, const float *w, bool nan, float *q)
-{
-    const float nanv = __uint_as_float(0x7fc00000u);
-    q[0] = nan ? nanv : sel_lerp(__uint_as_float(prefix[0]), __uint_as_float(prefix[1]), w[0]);
-    q[1] = nan ? nanv : sel_lerp(__uint_as_float(prefix[2]), __uint_as_float(prefix[3]), w[1]);
-}
+// what Regr3D selects: per (view, image) map m the ranks of q = 0.002 and q = 0.998 among |gt| of all n points
+struct PtSel {
+    const float *gt1, *gt2;
+    int B; long long n;
+    float *dis, *quant, *quant_out;      // quant_out: the caller's copy, may be null
+    __device__ SelPlan plan() const { return {{0.002f, 0.998f}, {SEL_ALL, SEL_ALL}}; }
+    __device__ float value(int m, long long i, int pass) const
+    {
+        float *dm = dis + (size_t)m * n;
+        if (pass) return dm[i];
+        const float *gt = m < B ? gt1 + (size_t)m * n * 3 : gt2 + (size_t)(m - B) * n * 3;      // (maps: view 1's B images, then view 2's)
+        return dm[i] = pt_dis(gt + 3 * i);
+    }
+    __device__ void finish(int m, const float *v, const float *w, bool nan) const
+    {
+        const float nanv = __uint_as_float(0x7fc00000u);
+        const float q0 = nan ? nanv : sel_lerp(v[0], v[1], w[0]), q1 = nan ? nanv : sel_lerp(v[2], v[3], w[1]);
+        quant[2 * m] = q0; quant[2 * m + 1] = q1;
+        if (quant_out) { quant_out[2 * m] = q0; quant_out[2 * m + 1] = q1; }
+    }
+};
 
 // ---- selection, small maps: one workgroup per map, keys in registers ----
-__global__ void __launch_bounds__(SEL_ONE_BLOCK) k_sel_one(const float *__restrict__ gt1, const float *__restrict__ gt2, int B, long long N,
-                                                           float *__restrict__ dis, uint32_t *__restrict__ nanflag, float *__restrict__ quant,
-                                                           float *__restrict__ quant_out)
+__global__ void __launch_bounds__(SEL_ONE_BLOCK) k_sel_one(PtSel s, uint32_t *__restrict__ nanflag)
 {
     __shared__ uint32_t h[SEL_RANKS * SEL_BINS];
     __shared__ uint32_t prefix[SEL_RANKS], left[SEL_RANKS];
     __shared__ uint32_t anynan;
-    const int m = blockIdx.x, view = m / B, b = m - view * B, tid = threadIdx.x, wave = tid >> 6;
-    const float *gt = (view ? gt2 : gt1) + (size_t)b * N * 3;
+    __shared__ float w[2];
+    const SelPlan pl = s.plan();
+    const int m = blockIdx.x, tid = threadIdx.x, wave = tid >> 6;
+    const long long N = s.n;
     uint32_t key[SEL_ONE_KEYS];
     bool nan = false;
 #pragma unroll
     for (int u = 0; u < SEL_ONE_KEYS; ++u) {
         const long long i = tid + (long long)u * SEL_ONE_BLOCK;
-        key[u] = 0u;
-        if (i < N) {
-            const float d = pt_dis(gt + 3 * i);
-            dis[(size_t)m * N + i] = d;
-            nan |= d != d;
-            key[u] = pt_key(d);
-        }
+        float d = 0.f;
+        if (i < N) { d = s.value(m, i, 0); nan |= d != d; }
+        key[u] = sel_key(d);
     }
-    float w[2];
     if (tid == 0) anynan = 0u;
-    if (tid < SEL_RANKS) { uint32_t k[SEL_RANKS]; sel_ranks(N, k, w); left[tid] = k[tid]; prefix[tid] = 0u; }
+    if (tid < SEL_RANKS) {
+        float wt;
+        left[tid] = sel_rank((tid >> 1) ? pl.q[1] : pl.q[0], (uint32_t)N, tid & 1, &wt);
+        prefix[tid] = 0u;
+        if (!(tid & 1)) w[tid >> 1] = wt;
+    }
     __syncthreads();
     if (nan) anynan = 1u;
     for (int pass = 0; pass < SEL_PASSES; ++pass) {
-        const int shift = 24 - 8 * pass;
         for (int t = tid; t < SEL_RANKS * SEL_BINS; t += SEL_ONE_BLOCK) h[t] = 0u;
         __syncthreads();
         if (pass == 0) {
@@ -136,99 +139,25 @@ __global__ void __launch_bounds__(SEL_ONE_BLOCK) k_sel_one(const float *__restri
             for (int u = 0; u < SEL_ONE_KEYS; ++u)
                 hist_bump_grouped(h, key[u] >> 24, tid + (long long)u * SEL_ONE_BLOCK < N);
         } else {
-            const uint32_t p0 = prefix[0] >> (shift + 8), p1 = prefix[1] >> (shift + 8), p2 = prefix[2] >> (shift + 8), p3 = prefix[3] >> (shift + 8);
+            const SelPrefixes p = sel_prefixes(prefix, 1, pass);
 #pragma unroll
             for (int u = 0; u < SEL_ONE_KEYS; ++u) {
-                if (tid + (long long)u * SEL_ONE_BLOCK >= N) continue;
-                const uint32_t top = key[u] >> (shift + 8), dg = (key[u] >> shift) & 255u;
-                if (top == p0) atomicAdd(h + dg, 1u);
-                if (top == p1) atomicAdd(h + SEL_BINS + dg, 1u);
-                if (top == p2) atomicAdd(h + 2 * SEL_BINS + dg, 1u);
-                if (top == p3) atomicAdd(h + 3 * SEL_BINS + dg, 1u);
+                const bool ok = tid + (long long)u * SEL_ONE_BLOCK < N;
+                sel_bump_ranks(h, key[u], p, ok, ok);
             }
         }
         __syncthreads();
         if (wave < SEL_RANKS) {
             uint32_t k = left[wave];
             const uint32_t d = sel_pick(h + (pass == 0 ? 0 : wave * SEL_BINS), k);
-            if ((tid & 63) == 0) { left[wave] = k; prefix[wave] |= d << shift; }
+            if ((tid & 63) == 0) { left[wave] = k; prefix[wave] |= d << (24 - 8 * pass); }
         }
         __syncthreads();
     }
     if (tid == 0) {
-        uint32_t k[SEL_RANKS];
-        float q[2];
-        sel_ranks(N, k, w);
-        sel_finish(prefix, w, anynan != 0u, q);
+        const float v[SEL_RANKS] = {sel_unkey(prefix[0]), sel_unkey(prefix[1]), sel_unkey(prefix[2]), sel_unkey(prefix[3])};
         nanflag[m] = anynan;
-        quant[2 * m] = q[0]; quant[2 * m + 1] = q[1];
-        if (quant_out) { quant_out[2 * m] = q[0]; quant_out[2 * m + 1] = q[1]; }
-    }
-}
-
-// ---- selection, large maps: a digit pass over (chunk, map) workgroups, then a pick per map ----
-__global__ void __launch_bounds__(PT_BLOCK) k_sel_hist(const float *__restrict__ gt1, const float *__restrict__ gt2, int B, long long N, int pass,
-                                                       float *__restrict__ dis, uint32_t *__restrict__ hist, const uint32_t *__restrict__ sel,
-                                                       uint32_t *__restrict__ nanflag)
-{
-    __shared__ uint32_t h[SEL_RANKS * SEL_BINS];
-    const int m = blockIdx.y, view = m / B, b = m - view * B, tid = threadIdx.x;
-    const long long per = (N + gridDim.x - 1) / gridDim.x, i0 = (long long)blockIdx.x * per, i1 = min(N, i0 + per);
-    const int rows = pass == 0 ? 1 : SEL_RANKS;
-    for (int t = tid; t < rows * SEL_BINS; t += PT_BLOCK) h[t] = 0u;
-    __syncthreads();
-    float *dm = dis + (size_t)m * N;
-    if (pass == 0) {
-        const float *gt = (view ? gt2 : gt1) + (size_t)b * N * 3;
-        bool nan = false;
-        for (long long base = i0; base < i1; base += PT_BLOCK) {       // (uniform trip count: the grouped bump is a wave-wide operation)
-            const long long i = base + tid;
-            const bool ok = i < i1;
-            float d = 0.f;
-            if (ok) { d = pt_dis(gt + 3 * i); dm[i] = d; nan |= d != d; }
-            hist_bump_grouped(h, pt_key(d) >> 24, ok);
-        }
-        if (nan) atomicOr(nanflag + m, 1u);
-    } else {
-        const int shift = 24 - 8 * pass;
-        const uint32_t *sp = sel + (size_t)m * SEL_RANKS * 2;
-        const uint32_t p0 = sp[0] >> (shift + 8), p1 = sp[2] >> (shift + 8), p2 = sp[4] >> (shift + 8), p3 = sp[6] >> (shift + 8);
-        for (long long i = i0 + tid; i < i1; i += PT_BLOCK) {
-            const uint32_t key = pt_key(dm[i]), top = key >> (shift + 8), dg = (key >> shift) & 255u;
-            if (top == p0) atomicAdd(h + dg, 1u);
-            if (top == p1) atomicAdd(h + SEL_BINS + dg, 1u);
-            if (top == p2) atomicAdd(h + 2 * SEL_BINS + dg, 1u);
-            if (top == p3) atomicAdd(h + 3 * SEL_BINS + dg, 1u);
-        }
-    }
-    __syncthreads();
-    uint32_t *hg = hist + (size_t)m * SEL_RANKS * SEL_BINS;
-    for (int t = tid; t < rows * SEL_BINS; t += PT_BLOCK)
-        if (h[t]) atomicAdd(hg + t, h[t]);
-}
-
-__global__ void __launch_bounds__(PT_BLOCK) k_sel_pick(long long N, int pass, uint32_t *__restrict__ hist, uint32_t *__restrict__ sel,
-                                                       const uint32_t *__restrict__ nanflag, float *__restrict__ quant, float *__restrict__ quant_out)
-{
-    __shared__ uint32_t prefix[SEL_RANKS];
-    const int m = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, shift = 24 - 8 * pass;
-    uint32_t *hg = hist + (size_t)m * SEL_RANKS * SEL_BINS, *sp = sel + (size_t)m * SEL_RANKS * 2;
-    uint32_t k0[SEL_RANKS];
-    float w[2];
-    sel_ranks(N, k0, w);
-    const uint32_t kw = wave == 0 ? k0[0] : (wave == 1 ? k0[1] : (wave == 2 ? k0[2] : k0[3]));     // (selects: a runtime index would put k0 in scratch)
-    uint32_t k = pass == 0 ? kw : sp[2 * wave + 1];
-    const uint32_t before = pass == 0 ? 0u : sp[2 * wave];
-    const uint32_t d = sel_pick(hg + (pass == 0 ? 0 : wave * SEL_BINS), k);
-    const uint32_t now = before | (d << shift);
-    if ((tid & 63) == 0) { sp[2 * wave] = now; sp[2 * wave + 1] = k; prefix[wave] = now; }
-    __syncthreads();
-    for (int t = tid; t < SEL_RANKS * SEL_BINS; t += PT_BLOCK) hg[t] = 0u;      // re-armed for the next pass (and the next call)
-    if (pass == SEL_PASSES - 1 && tid == 0) {
-        float q[2];
-        sel_finish(prefix, w, nanflag[m] != 0u, q);
-        quant[2 * m] = q[0]; quant[2 * m + 1] = q[1];
-        if (quant_out) { quant_out[2 * m] = q[0]; quant_out[2 * m + 1] = q[1]; }
+        s.finish(m, v, w, anynan != 0u);
     }
 }
 
@@ -451,21 +380,18 @@ __attribute__((visibility("default"))) int gsr_regr3d_fwd(const float *gt1, cons
     const int maps = 2 * B, chunks = pt_chunks(B, N);
     (void)hipGetLastError();
     if (!(dist_clip > 0.f)) {
+        const PtSel ps{gt1, gt2, B, (long long)N, sc.dis, sc.quant, quantiles};
         if (N <= SEL_ONE_MAX_N) {
-            hipLaunchKernelGGL(k_sel_one, dim3(maps), dim3(SEL_ONE_BLOCK), 0, s, gt1, gt2, B, (long long)N, sc.dis, sc.nanflag, sc.quant, quantiles);
+            hipLaunchKernelGGL(k_sel_one, dim3(maps), dim3(SEL_ONE_BLOCK), 0, s, ps, sc.sel.nanflag);
         } else {
-            // (histograms and NaN flags start at zero; the pick step re-arms the histograms after every pass)
-            if (!hip_ok(hipMemsetAsync(sc.hist, 0, reinterpret_cast<char *>(sc.quant) - reinterpret_cast<char *>(sc.hist), s))) return GSR_ELAUNCH;
-            for (int pass = 0; pass < SEL_PASSES; ++pass) {
-                hipLaunchKernelGGL(k_sel_hist, dim3(chunks, maps), dim3(PT_BLOCK), 0, s, gt1, gt2, B, (long long)N, pass, sc.dis, sc.hist, sc.sel, sc.nanflag);
-                hipLaunchKernelGGL(k_sel_pick, dim3(maps), dim3(PT_BLOCK), 0, s, (long long)N, pass, sc.hist, sc.sel, sc.nanflag, sc.quant, quantiles);
-            }
+            if (!hip_ok(hipMemsetAsync(sc.sel.hist, 0, sel_zero_bytes(sc.sel), s))) return GSR_ELAUNCH;
+            sel_run(ps, maps, chunks, sc.sel, s);
         }
     } else if (quantiles) {
         if (!hip_ok(hipMemsetAsync(quantiles, 0, (size_t)maps * 2 * 4, s))) return GSR_ELAUNCH;     // (dist_clip: no quantiles are taken)
     }
     hipLaunchKernelGGL(k_pt_mask, dim3(chunks, maps), dim3(PT_BLOCK), 0, s, a, sc.dis, sc.quant, sc.mask, valid, sc.part);
-    hipLaunchKernelGGL(k_pt_fold1, dim3(1), dim3(PT_BLOCK), 0, s, a, chunks, sc.part, sc.nanflag, sc.mapsum, sc.img, sc.glob, status, loss);
+    hipLaunchKernelGGL(k_pt_fold1, dim3(1), dim3(PT_BLOCK), 0, s, a, chunks, sc.part, sc.sel.nanflag, sc.mapsum, sc.img, sc.glob, status, loss);
     if (norm) {
         hipLaunchKernelGGL(k_pt_loss_norm, dim3(chunks, maps), dim3(PT_BLOCK), 0, s, a, sc.mask, sc.img, sc.part2);
         hipLaunchKernelGGL(k_pt_fold2, dim3(1), dim3(PT_BLOCK), 0, s, a, chunks, sc.part2, sc.glob, sc.mapsum + (size_t)maps * 4, sc.img, loss);

@@ -69,6 +69,17 @@ def test_selection_is_exact(N, B):
     assert not mask[nan_rows].any() and torch.isfinite(loss)
 
 
+def test_both_selection_paths_are_exact_on_a_shared_prefix():
+    """8 192 points of one row on the one-workgroup path, the same points and one more on the chunked path"""
+    d, gt = _z_rows(1, 8193, 77)
+    for n in (8192, 8193):
+        g = gt[:, :n].contiguous().to(DEV)
+        conf = torch.full((1, n), 5.0, device=DEV)
+        _, det = _hip(g, g, g + 0.1, g - 0.1, conf, conf)
+        want = torch.quantile(d[:, :n], Q, dim=1).t()
+        assert _same_bits(det["quantiles"].cpu(), torch.stack((want, want))), (n, det["quantiles"], want)
+
+
 def _clouds(seed=5, B=3, N=1536):
     g = torch.Generator().manual_seed(seed)
     gt1 = torch.randn(B, N, 3, generator=g) * 2

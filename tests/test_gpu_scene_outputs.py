@@ -150,6 +150,21 @@ def test_depth_range_cut_and_no_positive_depth():
     assert torch.equal(bits(got[1:]), bits(neg.quantile(0.99).log()[None]))            # (log of a non-positive quantile: NaN or -inf, as torch)
 
 
+def test_depth_range_with_a_nan_keeps_the_positive_quantile():
+    """a NaN is in "all depths" (q 0.99 and far are NaN, as torch) and not in "the positive ones" (q 0.01, near and the count ignore it)"""
+    d = _depths(501, 501)
+    d[7] = float("nan")
+    pos = d[d > 0]
+    assert torch.isfinite(pos.quantile(0.01)) and torch.isnan(d.quantile(0.99)) and _log_is_unambiguous(pos.quantile(0.01))
+    info = {}
+    got = ex.depth_range(d.to(DEV), details=info).cpu()
+    q = info["quantiles"].cpu()
+    print(f"[depth_range nan] near {float(got[0])!r} far {float(got[1])!r} quantiles {q.tolist()} status {info['status'].tolist()}")
+    assert torch.isnan(q[1]) and torch.isnan(got[1])
+    assert torch.equal(bits(q[:1]), bits(pos.quantile(0.01)[None])) and torch.equal(bits(got[:1]), bits(pos.quantile(0.01).log()[None]))
+    assert info["status"].tolist() == [int((d > 0).sum()), 0]
+
+
 # ---- gsr_pack_frames ----
 def test_pack_frames_bytes_equal_the_host_path_and_stay_inside_the_output():
     g = torch.Generator().manual_seed(11)
@@ -226,6 +241,17 @@ def test_ply_rows_and_normalizer_match_the_host_path(G_, d_sh):
             got, dnames = ex.ply_vertex_table(*dinp, shift_and_scale=shift, save_sh_dc_only=dc)
             assert dnames == names and got.is_cuda
             check_ply_table(got.cpu().numpy(), want.numpy(), f"G {G_} d_sh {d_sh} shift{int(shift)} dc{int(dc)}")
+
+
+def test_ply_normalizer_with_a_nan_on_one_axis():
+    """torch: the median of the axis that holds a NaN is NaN and so is the factor (max over the axes); the other two medians do not see it"""
+    means = _gaussians(65, 1, 6501)[0]
+    means[40, 1] = float("nan")
+    want = means.median(dim=0).values
+    assert torch.isnan(want[1]) and torch.isfinite(want[[0, 2]]).all() and torch.isnan((means - want).abs().quantile(0.95, dim=0).max())
+    got = ex.ply_normalizer(means.to(DEV)).cpu()
+    assert torch.equal(bits(got[[0, 2]]), bits(want[[0, 2]])), (got, want)
+    assert torch.isnan(got[1]) and torch.isnan(got[3]), got
 
 
 def test_ply_table_on_the_device_matches_the_reference_fixture():
