@@ -269,6 +269,30 @@ int gsr_mse_backward(const float *pred, const float *target, const float *grad_l
                      float *grad_pred, void *stream);
 
 /*
+ * Edge-aware depth smoothness, `LossDepth.forward` (src/loss/loss_depth.py:26-60), for N = b * v views, device fp32, contiguous:
+ *   n    = (max(min(depth, hi), lo) - lo) / (hi - lo) with lo = log(near[view]), hi = log(far[view]) -- the bounds are logs, the depth is
+ *          NOT logged: that is the reference's arithmetic and it is reproduced
+ *   t_x  = n[x+1] - n[x], or with second_derivative (n[x+2] - n[x+1]) - (n[x+1] - n[x]); t_y the same down the columns
+ *   image (N,3,H,W) given: t_x *= exp(-sigma_image * c_x), c_x = max over the channels of the SIGNED difference image[x+1] - image[x]
+ *          (second_derivative: the larger of the two neighbouring c_x); t_y likewise.  image NULL: no bilateral term, sigma_image unread
+ *   loss = weight * (mean |t_x| + mean |t_y|)     (the two means have N H (W-k) and N (H-k) W elements, k = 1 or 2)
+ * fwd: one pass + a one-workgroup fold of per-workgroup float64 partials in a fixed order: two launches, no atomics, bit-identical from
+ *      run to run.  bwd: one launch in gather form, every element of grad_depth (N,H,W) written exactly once, nothing to zero:
+ *      dL/ddepth = weight * grad_loss[0] / count_axis / (hi - lo) * (sum of the signs x weights of the differences the pixel is part of)
+ *      * (1 inside the bounds, 1/2 exactly at a bound, 0 outside: torch's minimum / maximum), with sign(0) = 0.  grad_loss: device fp32[1],
+ *      NULL = 1.  lo, hi, 1 / (hi - lo) in float64 from the fp32 near / far, per-pixel arithmetic fp32.  Rows need no alignment.
+ * scratch: device memory of gsr_depth_smooth_scratch_bytes() (0 for invalid dimensions), no initialisation, not shared between
+ * concurrent calls.  GSR_EINVAL before any launch: N < 1, H or W < 2 (< 3 with second_derivative; the reference returns NaN, the mean
+ * of an empty tensor), more than 2^24 - 1 tiles of 128 x 8 pixels, NULL depth / near / far / loss / grad_depth / scratch.
+ */
+size_t gsr_depth_smooth_scratch_bytes(int64_t N, int H, int W);
+int gsr_depth_smooth_fwd(const float *depth, const float *image, const float *near, const float *far, int64_t N, int H, int W,
+                         float weight, float sigma_image, int second_derivative, void *scratch, float *loss, void *stream);
+int gsr_depth_smooth_bwd(const float *depth, const float *image, const float *near, const float *far, const float *grad_loss,
+                         int64_t N, int H, int W, float weight, float sigma_image, int second_derivative, float *grad_depth,
+                         void *stream);
+
+/*
  * Image scores of the test step (src/evaluation/metrics.py:11-52) for N image pairs (N,C,H,W), device fp32, contiguous:
  *   ssim[n] = mean over c of skimage structural_similarity(gt[n], pred[n], win_size=11, gaussian_weights=True, channel_axis=0,
  *             data_range=1.0): Gaussian window sigma 1.5 / radius 5, sample covariance (x 121/120), C1 = 1e-4, C2 = 9e-4, the map

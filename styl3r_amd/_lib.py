@@ -18,7 +18,7 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip", "gsr_depth.hip"]
 _HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
@@ -132,7 +132,8 @@ EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_f
            "gsr_k6_blocks_per_cu", "gsr_test_reduce9",
            "gsr_trajectory", "gsr_outputs_scratch_bytes", "gsr_depth_range", "gsr_pack_frames", "gsr_ply_normalizer", "gsr_ply_rows",
            "gsr_resample_plan", "gsr_resample_scratch_bytes", "gsr_resample_crop",
-           "gsr_view_overlap_scratch_bytes", "gsr_view_overlap", "gsr_draw_layers", "gsr_undistort")
+           "gsr_view_overlap_scratch_bytes", "gsr_view_overlap", "gsr_draw_layers", "gsr_undistort",
+           "gsr_depth_smooth_scratch_bytes", "gsr_depth_smooth_fwd", "gsr_depth_smooth_bwd")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -235,6 +236,12 @@ def load() -> C.CDLL:
     lib.gsr_draw_layers.restype = C.c_int
     lib.gsr_undistort.argtypes = [vp, i64, C.c_int, C.c_int, vp, C.c_int, vp, C.c_int, C.c_int, vp, vp]
     lib.gsr_undistort.restype = C.c_int
+    lib.gsr_depth_smooth_scratch_bytes.argtypes = [i64, C.c_int, C.c_int]
+    lib.gsr_depth_smooth_scratch_bytes.restype = C.c_size_t
+    lib.gsr_depth_smooth_fwd.argtypes = [vp, vp, vp, vp, i64, C.c_int, C.c_int, f32, f32, C.c_int, vp, vp, vp]
+    lib.gsr_depth_smooth_fwd.restype = C.c_int
+    lib.gsr_depth_smooth_bwd.argtypes = [vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, f32, f32, C.c_int, vp, vp]
+    lib.gsr_depth_smooth_bwd.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

@@ -24,9 +24,10 @@ ap.add_argument("--config", choices=["c3", "c4", "c5"], default="c3",
                 help="c3: NVS-pretrain, 2 ctx / 4 tgt views, MSE, everything trains.  c4: style stage, 4 ctx / 6 tgt views, "
                      "VGG style loss + identity pass (two encoder/decoder passes), backbone frozen (random-init VGG: no weights here).  "
                      "c5: stress shapes, 4 ctx views 512x512 -> 1 048 576 Gaussians/scene, sh_degree 4, 4 tgt views 512x512, MSE, all train")
-ap.add_argument("--extra-losses", choices=["lpips"], default=None,
+ap.add_argument("--extra-losses", choices=["lpips", "depth"], default=None,
                 help="lpips: also time the step with the reference's `/loss: [mse, lpips]` (TrainStep extra_losses=[LossLpips()], LPIPS-VGG on the "
-                     "HIP route, random-init weights), in the same process right after the MSE-only step; reported under `with_lpips`")
+                     "HIP route, random-init weights), in the same process right after the MSE-only step; reported under `with_lpips`.  "
+                     "depth: the same with `/loss: [mse, depth]` (extra_losses=[LossDepth()], config/loss/depth.yaml's values); reported under `with_depth`")
 args = ap.parse_args()
 assert not (args.extra_losses and args.config == "c4"), "--extra-losses: the c4 step lists its own losses (LossStyle + identity), not the default MSE"
 if args.linear_mode:
@@ -88,6 +89,22 @@ if args.extra_losses == "lpips":
     with_lpips = {"losses": "[mse, lpips] (mse fused in the composite kernels, LPIPS-VGG weight 0.05)",
                   "value": round(dist_utils.aggregate_throughput(b * v_tgt, args.steps, world, dt_l), 3), "unit": "views/s",
                   "ms_per_step": round(1e3 * dt_l / args.steps, 2), "peak_mem_GB": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1)}
+with_depth = None
+if args.extra_losses == "depth":
+    from styl3r_amd import losses as _losses
+    step.extra_losses = [_losses.LossDepth()]                      # same step object: the same encoder, optimizer state and batch
+    torch.cuda.reset_peak_memory_stats(dev)
+    n0 = _losses.CALLS["depth_hip_bwd"]
+    for _ in range(args.warmup):
+        step(batch)
+    assert _losses.CALLS["depth_hip_bwd"] > n0, "the depth loss did not take the HIP route"
+    dt_d = dist_utils.timed_steps(lambda: step(batch), args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)
+    step.extra_losses = []
+    dt_again = dist_utils.timed_steps(lambda: step(batch), args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)      # A / B / A: the spread of the MSE-only step
+    with_depth = {"losses": "[mse, depth] (mse fused in the composite kernels, LossDepth weight 0.25, first derivative, no bilateral term)",
+                  "value": round(dist_utils.aggregate_throughput(b * v_tgt, args.steps, world, dt_d), 3), "unit": "views/s",
+                  "ms_per_step": round(1e3 * dt_d / args.steps, 2), "mse_only_again_ms_per_step": round(1e3 * dt_again / args.steps, 2),
+                  "peak_mem_GB": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1)}
 if rank == 0:
     nparam = sum(p.numel() for p in enc.parameters())
     print(json.dumps({"metric": ("512x512" if c5 else "256x256") + " rendered views/sec, full train step (encoder+rasterizer fwd+bwd, AdamW, DP all-reduce)",
@@ -99,6 +116,7 @@ if rank == 0:
                       "grad_bytes": 4 * sum(p.numel() for p in enc.parameters() if p.requires_grad),
                       "buckets": len(step.reducer.buckets), "peak_mem_GB": round(peak_mse / 2**30, 1),
                       "dtype": "f32", "linear_arithmetic": __import__("styl3r_amd.vit_ops", fromlist=["x"]).LINEAR_MODE
-, "data": "synthetic, random-init weights", **({"with_lpips": with_lpips} if with_lpips else {})}))
+, "data": "synthetic, random-init weights", **({"with_lpips": with_lpips} if with_lpips else {}),
+                      **({"with_depth": with_depth} if with_depth else {})}))
 if dist is not None:
     dist.barrier(); dist.destroy_process_group()
