@@ -522,6 +522,78 @@ int gsr_undistort(const uint8_t *src, int64_t N, int H, int W, const double *cam
                   int roi_h, uint8_t *dst, void *stream);
 
 /*
+ * JPEG frames (csrc/gsr_jpeg_entropy.h on the host, csrc/gsr_jpeg.hip on the device; the reference's loader decodes one frame at a
+ * time with PIL, src/dataset/dataset_re10k_style.py::convert_images).  The Huffman stage is serial per image and stays on the host; the
+ * rest -- dequantisation, the "islow" integer IDCT, fancy chroma upsampling, YCbCr -> RGB -- is integer arithmetic per pixel and runs
+ * on the device.  The bytes are those of libjpeg-turbo (JDCT_ISLOW, fancy upsampling), bit for bit.
+ *
+ * Fast path: SOF0 / SOF1, 8-bit samples, Huffman coding, ONE interleaved scan; one component, or three (YCbCr: a JFIF marker, or no
+ * Adobe marker, or Adobe transform 1) with luma sampled 1x1, 2x1 or 2x2 and chroma 1x1; any restart interval, any Huffman tables.
+ * A valid stream outside it (progressive, arithmetic, 12-bit, CMYK / YCCK, RGB, 4:4:0, 4:1:1, several scans, 16-bit tables in SOF0) is
+ * GSR_JPEG_UNSUPPORTED, and so is an image one of whose dequantised 8 x 8 blocks fails the coefficient gate: the sum of |coef * q|
+ * over a column above GSR_JPEG_MAX_COLUMN_L1, or over the block above GSR_JPEG_MAX_BLOCK_L1 (inside the gate neither
+ * the kernel's 32-bit arithmetic nor the 16-bit lanes of the reference's SIMD code can overflow; uniform noise encoded at quality
+ * 100 reaches about a third of the column bound and a quarter of the block bound).  A truncated or invalid stream is GSR_JPEG_CORRUPT.  The stream is untrusted: no read
+ * outside [data, data + len), no write outside the image's coefficient region, whatever the bytes say.
+ *
+ * jpeg_probe (HOST ONLY): the markers up to the scan header.  info->width / height / components are filled as far as a frame header
+ *     was read, sampling is a GSR_JPEG_* class for GSR_OK and -1 otherwise.  Returns GSR_OK, GSR_JPEG_UNSUPPORTED, GSR_JPEG_CORRUPT,
+ *     or GSR_EINVAL for a null pointer.
+ * jpeg_entropy (HOST ONLY, no device call): N streams of ONE picture size H x W -> coefficient blocks.  coefs: jpeg_coef_bytes(N, H, W)
+ *     bytes of host memory (pinned by the caller when a device is the target).  Image n owns desc[n].coef_count int16 values from
+ *     coefs + desc[n].coef_offset, the images one behind the other (the used prefix ends at the last image's offset + count):
+ *     component after component, each a grid of bw[c] x bh[c] blocks in whole MCUs, row-major, every block 64 coefficients in natural
+ *     (de-zigzagged, row-major) order, zero where the stream coded none.  desc[n].quant[c] is component c's quantisation table in
+ *     natural order.  status[n] is GSR_OK, GSR_JPEG_UNSUPPORTED or GSR_JPEG_CORRUPT per image (then desc[n].sampling = -1, count 0);
+ *     one bad image does not fail the call.  threads is clamped to [1, 16] and to N; the images are independent.
+ *     GSR_EINVAL before any work: null pointers, N < 1 or > 2^24, H or W outside [1, 65535].
+ * jpeg_pixels: the device stage.  coefs_dev / desc_dev are the arrays above on the device (coefs 16-byte aligned -- every block
+ *     then is --, desc 8-byte aligned); out is (N,H,W,3) interleaved bytes, 4-byte aligned: the layout gsr_resample_crop reads.  Images
+ *     of one call may differ in sampling class and tables.  An image whose desc[n].sampling is negative is written as zeros.
+ *     scratch: jpeg_scratch_bytes(N, H, W) of device memory, 16-byte aligned, uninitialised (the byte planes between the launches; 0 for
+ *     invalid dimensions).  The descriptors are the caller's: block grids and offsets are checked against H, W and the scratch
+ *     size ON THE DEVICE before they are used, and an image that fails is written as zeros.  Two launches (IDCT to byte planes;
+ *     upsampling + colour), no atomics, no host sync, every output byte written exactly once.
+ *       dequantise  coef * q
+ *       IDCT        8 x 8 "islow": CONST_BITS 13, PASS1_BITS 2; columns first, descaled by 11 with rounding; then rows, descaled by 18
+ *       range       s = v & 1023, s -= 1024 if s >= 512, byte = clamp(s + 128, 0, 255)
+ *       upsample    cw = ceil(W / 2) chroma columns (ch likewise).  cw <= 2: replication.  h2v1: out[2i] = (3 in[i] + in[i-1] + 1) >> 2,
+ *                   out[2i+1] = (3 in[i] + in[i+1] + 2) >> 2, the two ends copied.  h2v2: cs = 3 row + neighbour row (above for even
+ *                   output rows, below for odd ones, clamped to [0, ch - 1]); out[2i] = (3 cs[i] + cs[i-1] + 8) >> 4,
+ *                   out[2i+1] = (3 cs[i] + cs[i+1] + 7) >> 4, ends (4 cs[0] + 8) >> 4 and (4 cs[cw-1] + 7) >> 4
+ *       colour      cb -= 128, cr -= 128; R = Y + ((91881 cr + 32768) >> 16), B = Y + ((116130 cb + 32768) >> 16),
+ *                   G = Y + ((-22554 cb - 46802 cr + 32768) >> 16), clamped; one component: R = G = B = Y
+ *     GSR_EINVAL before any launch: null pointers, misaligned coefs / desc / scratch / out, N < 1 or > 2^24, H or W outside
+ *     [1, 65535]; GSR_ENOSPACE: scratch too small.
+ */
+#define GSR_JPEG_UNSUPPORTED 1
+#define GSR_JPEG_CORRUPT 2
+#define GSR_JPEG_GRAY 0
+#define GSR_JPEG_444 1
+#define GSR_JPEG_422 2
+#define GSR_JPEG_420 3
+#define GSR_JPEG_MAX_COLUMN_L1 5888
+#define GSR_JPEG_MAX_BLOCK_L1 14080
+typedef struct gsr_jpeg_info {
+    int32_t width, height, components, sampling, restart_interval;
+} gsr_jpeg_info;
+typedef struct gsr_jpeg_desc {
+    int32_t sampling;      /* GSR_JPEG_GRAY / _444 / _422 / _420; negative: not decoded */
+    int32_t ncomp;         /* 1 or 3 */
+    int32_t bw[3], bh[3];  /* blocks per row / block rows of each component, whole MCUs */
+    int64_t coef_offset;   /* int16 values from `coefs` to component 0, block 0 */
+    int64_t coef_count;    /* int16 values of all components */
+    uint16_t quant[3][64]; /* per component, natural order */
+} gsr_jpeg_desc;
+int gsr_jpeg_probe(const uint8_t *data, size_t len, gsr_jpeg_info *info);
+size_t gsr_jpeg_coef_bytes(int64_t N, int H, int W);
+int gsr_jpeg_entropy(const uint8_t *const *data, const size_t *len, int64_t N, int H, int W, int16_t *coefs, gsr_jpeg_desc *desc,
+                     int32_t *status, int threads);
+size_t gsr_jpeg_scratch_bytes(int64_t N, int H, int W);
+int gsr_jpeg_pixels(const int16_t *coefs_dev, const gsr_jpeg_desc *desc_dev, int64_t N, int H, int W, void *scratch, size_t scratch_bytes,
+                    uint8_t *out, void *stream);
+
+/*
  * gsr_draw_layers (validation visuals; the reference's src/visualization/drawing/): anti-aliased lines and points drawn over B planar
  * fp32 images (B,3,H,W) on the device, `out` = `images` for in-place.  Image b carries the ordered layers image_layers[b] ..
  * image_layers[b + 1] - 1 (int32 (B + 1,)); layer l carries the records layer_prims[l] .. layer_prims[l + 1] - 1 (int32 (NL + 1,)) and is

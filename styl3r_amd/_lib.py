@@ -18,8 +18,8 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip", "gsr_depth.hip"]
-_HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "../../include/gsr.h"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip", "gsr_depth.hip", "gsr_jpeg.hip"]
+_HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "gsr_jpeg_entropy.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
     "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -101,6 +101,17 @@ class GsrFused(C.Structure):
                 ("mse_grad_loss", C.c_void_p)]
 
 
+class GsrJpegInfo(C.Structure):
+    """include/gsr.h gsr_jpeg_info: what gsr_jpeg_probe reads from the markers in front of the scan"""
+    _fields_ = [(n, C.c_int32) for n in ("width", "height", "components", "sampling", "restart_interval")]
+
+
+class GsrJpegDesc(C.Structure):
+    """include/gsr.h gsr_jpeg_desc: sampling class, block grids, coefficient region and quantisation tables of one decoded image"""
+    _fields_ = [("sampling", C.c_int32), ("ncomp", C.c_int32), ("bw", C.c_int32 * 3), ("bh", C.c_int32 * 3),
+                ("coef_offset", C.c_int64), ("coef_count", C.c_int64), ("quant", (C.c_uint16 * 64) * 3)]
+
+
 GSR_FLAG_NTOUCHED = 1
 GSR_FLAG_COV9 = 2
 GSR_FLAG_PHASE_BIN = 4
@@ -122,6 +133,9 @@ GSR_PT_EMPTY_MAP, GSR_PT_NAN, GSR_PT_EMPTY_VIEW = 1, 2, 4     # status bits of g
 GSR_DRAW_RECORD_DOUBLES, GSR_DRAW_CHUNK = 16, 32                    # gsr_draw_layers: doubles per record, records per LDS chunk
 GSR_DRAW_BUTT, GSR_DRAW_ROUND, GSR_DRAW_SQUARE, GSR_DRAW_POINT = 0, 1, 2, 3
 GSR_UNDISTORT_CAM_DOUBLES, GSR_UNDISTORT_FRAMES_PER_LAUNCH = 16, 1024     # gsr_undistort: doubles per camera row, frames per launch
+GSR_JPEG_UNSUPPORTED, GSR_JPEG_CORRUPT = 1, 2                  # status of gsr_jpeg_probe / gsr_jpeg_entropy (GSR_OK = 0)
+GSR_JPEG_GRAY, GSR_JPEG_444, GSR_JPEG_422, GSR_JPEG_420 = 0, 1, 2, 3
+GSR_JPEG_MAX_COLUMN_L1, GSR_JPEG_MAX_BLOCK_L1 = 5888, 14080     # the coefficient gate
 GSR_DEPTH_NO_POSITIVE = 1                                     # status[1] of gsr_depth_range
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_fused", "gsr_backward_fused", "gsr_version", "gsr_profile_create",
@@ -133,7 +147,8 @@ EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_f
            "gsr_trajectory", "gsr_outputs_scratch_bytes", "gsr_depth_range", "gsr_pack_frames", "gsr_ply_normalizer", "gsr_ply_rows",
            "gsr_resample_plan", "gsr_resample_scratch_bytes", "gsr_resample_crop",
            "gsr_view_overlap_scratch_bytes", "gsr_view_overlap", "gsr_draw_layers", "gsr_undistort",
-           "gsr_depth_smooth_scratch_bytes", "gsr_depth_smooth_fwd", "gsr_depth_smooth_bwd")
+           "gsr_depth_smooth_scratch_bytes", "gsr_depth_smooth_fwd", "gsr_depth_smooth_bwd",
+           "gsr_jpeg_probe", "gsr_jpeg_coef_bytes", "gsr_jpeg_entropy", "gsr_jpeg_scratch_bytes", "gsr_jpeg_pixels")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -242,6 +257,16 @@ def load() -> C.CDLL:
     lib.gsr_depth_smooth_fwd.restype = C.c_int
     lib.gsr_depth_smooth_bwd.argtypes = [vp, vp, vp, vp, vp, i64, C.c_int, C.c_int, f32, f32, C.c_int, vp, vp]
     lib.gsr_depth_smooth_bwd.restype = C.c_int
+    lib.gsr_jpeg_probe.argtypes = [vp, sz, C.POINTER(GsrJpegInfo)]
+    lib.gsr_jpeg_probe.restype = C.c_int
+    lib.gsr_jpeg_coef_bytes.argtypes = [i64, C.c_int, C.c_int]
+    lib.gsr_jpeg_coef_bytes.restype = C.c_size_t
+    lib.gsr_jpeg_entropy.argtypes = [C.POINTER(vp), C.POINTER(sz), i64, C.c_int, C.c_int, vp, vp, vp, C.c_int]
+    lib.gsr_jpeg_entropy.restype = C.c_int
+    lib.gsr_jpeg_scratch_bytes.argtypes = [i64, C.c_int, C.c_int]
+    lib.gsr_jpeg_scratch_bytes.restype = C.c_size_t
+    lib.gsr_jpeg_pixels.argtypes = [vp, vp, i64, C.c_int, C.c_int, vp, sz, vp, vp]
+    lib.gsr_jpeg_pixels.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

@@ -17,8 +17,8 @@ The rules (PIL's 8-bit resize, restated):
   float      float32(double(byte) / 255)
   flip       at the source read, before the filter (the reference reflects before it rescales; plans and crop offsets are not symmetric)
 
-Reading `.torch` chunks, decoding JPEGs, undistortion and the COLMAP parsers stay with the caller; the view samplers are in
-styl3r_amd/views.py and `example_from_scene` runs one in front of `prepare_example`.
+Reading `.torch` chunks and decoding their JPEG frames is styl3r_amd/dataset.py, undistortion and the COLMAP parsers
+styl3r_amd/colmap.py; the view samplers are in styl3r_amd/views.py and `example_from_scene` runs one in front of `prepare_example`.
 """
 from __future__ import annotations
 
@@ -384,7 +384,7 @@ def _to_device(frames: Tensor, device) -> Tensor:
 
 def prepare_example(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, context_indices, target_indices, style, cfg: InputCfg, *,
                     stage: str, pixel_intrinsics: bool = False, flip: Optional[bool] = None, scene: str = "", device=None,
-                    generator: Optional[torch.Generator] = None) -> dict:
+                    generator: Optional[torch.Generator] = None, preselected: bool = False) -> dict:
     """Decoded frames + raw cameras of one scene -> the example dict of the reference's dataset/types.py:
     context / target (extrinsics, intrinsics, image, near, far, index), scene, style {"image"}.
       frames       uint8 (n,H,W,3) or float (n,3,H,W), all frames of the scene the indices point into.  CPU bytes are uploaded as bytes
@@ -392,6 +392,8 @@ def prepare_example(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, cont
       intrinsics   (n,3,3), normalised, or in pixels with pixel_intrinsics=True; extrinsics (n,4,4) c2w
       style        one image, uint8 (Hs,Ws,3) or float (3,Hs,Ws); None: no "style" entry
       flip         None: the augmentation draw (one torch.rand(()) from `generator`) when stage == "train" and cfg.augment; else as given
+      preselected  `frames` holds exactly the context frames followed by the target frames (styl3r_amd.dataset decodes no others); the
+                   indices still name the scene's frames and cameras, and the "index" entries carry them
     In the order of the reference's loader: (1) pixel K / (w, h); (2) the FOV gate over all n cameras; (3) baseline-1 scaling of all
     translations with the range gate; (4) camera_normalization against the first context view; (5) near / far over the scale; (6) the
     reflection; (7) the crop shim.  The gates raise SkipExample.  Cameras are computed on the host in float64 (`prepare_cameras_f64`, the
@@ -403,8 +405,13 @@ def prepare_example(frames: Tensor, intrinsics: Tensor, extrinsics: Tensor, cont
     if flip is None:
         flip = bool(stage == "train" and cfg.augment and not (torch.rand(tuple(), generator=generator) < 0.5))
     cams = prepare_cameras_f64(intrinsics, extrinsics, ci.tolist(), ti.tolist(), cfg, (h, w), pixel_intrinsics, bool(flip))
-    sel = torch.cat([ci, ti]).to(frames.device)
-    picked = _to_device(frames.index_select(0, sel), device)
+    if preselected:
+        if frames.shape[0] != len(ci) + len(ti):
+            raise ValueError(f"prepare_example: {frames.shape[0]} preselected frames for {len(ci)} context and {len(ti)} target views")
+        picked = _to_device(frames, device)
+    else:
+        sel = torch.cat([ci, ti]).to(frames.device)
+        picked = _to_device(frames.index_select(0, sel), device)
     dev = picked.device
     images, _ = rescale_and_crop(picked, torch.zeros(3, 3), tuple(cfg.input_image_shape), flip=bool(flip))
     # the eight camera arrays travel in ONE upload and are handed out as views of it; the indices in a second one
