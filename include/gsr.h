@@ -594,6 +594,38 @@ int gsr_jpeg_pixels(const int16_t *coefs_dev, const gsr_jpeg_desc *desc_dev, int
                     uint8_t *out, void *stream);
 
 /*
+ * PNG frames (csrc/gsr_png.hip; the reference's src/misc/image_io.py saves every picture through PIL): N pictures of one size H x W with
+ * C = 3 or 4 channels -> the zlib stream of each picture's IDAT chunk, on the device.  A picture is cut into chunks of whole rows, the most
+ * rows whose filtered bytes rows * (1 + W * C) fit GSR_PNG_CHUNK_BYTES; one workgroup codes one chunk, all chunks of all pictures in one launch.
+ *
+ * png_chunks: src is GSR_PNG_SRC_U8 -- uint8 (N,H,W,C) interleaved -- or GSR_PNG_SRC_F32_PLANAR -- fp32 (N,C,H,W), converted in the load
+ *     as (clip(x, 0, 1) * 255) truncated, NaN -> 0.  filter_mode 0: per row the PNG filter 0..4 with the smallest sum of min(b, 256 - b) over
+ *     the filtered bytes, ties to the lowest number (the row above the first is zeros); 1: filter 0 on every row.  Tokens are byte runs
+ *     only (distance 1, zlib's Z_RLE); the literal / length code is a 15-bit-limited Huffman code built as the head of gsr_png.hip states,
+ *     sent with the repeat codes 16 / 17 / 18; the block is BTYPE 2, BFINAL 0, followed by an empty stored block, or -- when that is not
+ *     smaller than the chunk's bytes + 5 -- one stored block.  Per chunk the scratch receives the payload, its size and the Adler-32 partial.
+ * png_assemble: per picture `78 01`, the payloads, `01 00 00 FF FF`, the Adler-32 big-endian, at out + n * out_stride
+ *     (out_stride >= png_stream_bound); lengths[n] = bytes of the stream (int32).  Bytes beyond the length are not written.
+ * scratch: png_scratch_bytes(N, H, W, C) of device memory, 16-byte aligned, uninitialised; the same buffer for both calls.
+ * png_scratch_bytes / png_stream_bound return 0 for sizes the calls refuse.  No atomics on global memory, no read-back, two launches.
+ * Returns GSR_OK; GSR_PNG_ROW_TOO_WIDE when 1 + W * C > GSR_PNG_CHUNK_BYTES (nothing is launched; the caller's fallback encodes it);
+ * GSR_EINVAL before any launch: null pointers, N < 1 or > 2^24, H or W < 1 or > 2^20, C not 3 or 4, an unknown src_kind / filter_mode,
+ * scratch not 16-byte aligned, fp32 src or lengths not 4-byte aligned, a stream bound above 2^31 - 1, out_stride below the bound;
+ * GSR_ENOSPACE: scratch_bytes too small.
+ */
+#define GSR_PNG_CHUNK_BYTES 16384 /* at most 65535: a chunk can always be one stored block */
+#define GSR_PNG_SLOT_BYTES (GSR_PNG_CHUNK_BYTES + 8) /* scratch per chunk payload (worst case chunk + 5, rounded for word stores) */
+#define GSR_PNG_SRC_U8 0
+#define GSR_PNG_SRC_F32_PLANAR 1
+#define GSR_PNG_ROW_TOO_WIDE 1
+size_t gsr_png_scratch_bytes(int64_t N, int H, int W, int C);
+size_t gsr_png_stream_bound(int H, int W, int C);
+int gsr_png_chunks(const void *src, int src_kind, int64_t N, int H, int W, int C, int filter_mode, void *scratch, size_t scratch_bytes,
+                   void *stream);
+int gsr_png_assemble(const void *scratch, size_t scratch_bytes, int64_t N, int H, int W, int C, uint8_t *out, size_t out_stride,
+                     int32_t *lengths, void *stream);
+
+/*
  * gsr_draw_layers (validation visuals; the reference's src/visualization/drawing/): anti-aliased lines and points drawn over B planar
  * fp32 images (B,3,H,W) on the device, `out` = `images` for in-place.  Image b carries the ordered layers image_layers[b] ..
  * image_layers[b + 1] - 1 (int32 (B + 1,)); layer l carries the records layer_prims[l] .. layer_prims[l + 1] - 1 (int32 (NL + 1,)) and is

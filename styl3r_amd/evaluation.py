@@ -8,7 +8,8 @@ Deviations from the reference:
   * The encoder runs under `no_grad` and its `requires_grad` flags are left alone (the reference sets them all False and switches the
     encoder to eval mode in test_step_align; nothing trains here, and the caller owns the module's mode).
   * LPIPS scores mean something only with learned weights: `scores["lpips_weights_loaded"]` says whether the module had them.
-Dataset loading, the evaluation index, saving images / videos / comparisons and logging stay with the caller.
+  * `test.save_image` is off by default (the reference's main.yaml turns it on): nothing is written unless the caller asks.
+Dataset loading, the evaluation index, saving videos / comparisons and logging stay with the caller.
 
 `estimate_relative_pose` (below) is the reference's other evaluation, `PoseEvaluator.test_step` (src/evaluation/pose_evaluator.py:48-164): the
 pose of the context views relative to the first from a PnP-RANSAC initialisation and the same alignment loop with the SSIM-structure term added.
@@ -17,7 +18,8 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from pathlib import Path
+from typing import Optional, Sequence, Union
 
 import torch
 
@@ -36,6 +38,25 @@ class TestCfg:
     rot_opt_lr: float = 0.005
     trans_opt_lr: float = 0.005
     compute_scores: bool = True
+    save_image: bool = False                     # write the rendered target views as <output_path>/<scene>/color/<index:0>6>.png
+    output_path: Union[str, Path] = "outputs/test"
+
+
+def save_color_images(cfg: TestCfg, batch: dict, output) -> list:
+    """model_wrapper_style.py:366-372 for b >= 1 scenes: the rendered colours of scene i under `cfg.output_path / batch["scene"][i] / color`,
+    named by the target indices; one `image_io.save_images` call (one encoder call) per scene.  Returns the paths written."""
+    from .image_io import save_images
+    scenes = batch["scene"]
+    scenes = [scenes] if isinstance(scenes, str) else list(scenes)
+    index = batch["target"]["index"]
+    if len(scenes) != output.color.shape[0]:
+        raise ValueError(f"save_color_images: {len(scenes)} scene names for {output.color.shape[0]} scenes")
+    written = []
+    for i, scene in enumerate(scenes):
+        paths = [Path(cfg.output_path) / scene / f"color/{int(k):0>6}.png" for k in index[i]]
+        save_images(output.color[i].detach(), paths)
+        written += paths
+    return written
 
 
 def align_target_poses(decoder, gaussians, batch: dict, losses: Sequence, cfg: TestCfg, global_step: int = 0):
@@ -86,7 +107,8 @@ def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = Te
               style: Optional[dict] = None, global_step: int = 0):
     """test_step (:317-364) for b >= 1 scenes.  Returns (DecoderOutput of the (aligned) target views, scores): scores has the reference's
     keys `psnr_ours`, `ssim_ours`, `lpips_ours` -- each the mean over a scene's target views, shape (b,) -- and `lpips_weights_loaded`;
-    empty when `cfg.compute_scores` is off."""
+    empty when `cfg.compute_scores` is off.  With `cfg.save_image` the rendered views are also written as PNG files (`save_color_images`;
+    `batch["scene"]` and `batch["target"]["index"]` name them)."""
     tgt = batch["target"]
     b, v, _, h, w = tgt["image"].shape
     style = style if style is not None else {"image": batch["context"]["image"][:, 0]}
@@ -95,6 +117,8 @@ def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = Te
     extrinsics = align_target_poses(decoder, gaussians, batch, losses, cfg, global_step)[0] if cfg.align_pose else tgt["extrinsics"]
     with torch.no_grad():
         output = decoder.forward(gaussians, extrinsics, tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
+    if cfg.save_image:
+        save_color_images(cfg, batch, output)
     if not cfg.compute_scores:
         return output, {}
     gt, pred = tgt["image"].reshape(b * v, -1, h, w), output.color.reshape(b * v, -1, h, w)

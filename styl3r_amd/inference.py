@@ -8,8 +8,8 @@ through ONE `restyle` batch, and the plain + S stylized sets -- which share mean
 `forward_styles` call.  `prepare_scene` is the other end: decoded frames and raw cameras in, the (context, styles, target) that
 `stylize_scene` takes out, images rescaled and cropped on the device (inputs.py); `prepare_colmap_scene` is the same end for a COLMAP
 capture loaded by `colmap.load_colmap_scene` (infer_model_colmap.py), its frames undistorted on the device first.  `render_flythrough` turns the result into the frames of the drivers' videos (render_video_generic and the
-wrapper's three trajectories) and `export_scene_ply` into their .ply files; encoding a container, decoding the frames and the
-dataset readers stay with the caller.
+wrapper's three trajectories), `export_scene_ply` into their .ply files and `save_scene_images` into their tree of PNG files;
+encoding a video container stays with the caller.
 
     context, styles, target = prepare_scene(frames_u8, K, c2w, [0, 40], range(0, 41, 5), [style_a, style_b], device="cuda")
     scene = stylize_scene(encoder, decoder, context, styles, target)
@@ -211,3 +211,25 @@ def export_scene_ply(scene: StylizedScene, directory, shift_and_scale: bool = Fa
                    save_sh_dc_only=save_sh_dc_only)
         paths.append(directory / name)
     return paths
+
+
+def save_scene_images(output_dir, scene: str, style_image_name: str, batch: dict, output, stylized_output) -> list:
+    """infer_model_re10k.py:505-535: the picture tree of one stylized scene under `output_dir / f"{scene} | {style_image_name[:-4]}"` --
+    the style image under `batch["style"]["image_name"]` (its own suffix: Pillow unless it is .png), then `context/`, `target/`, `color/`
+    and `stylized_color/`, every file `<index:0>6>.png`; context images go through the inverse normalisation (x * 0.5 + 0.5) first.
+    `output` / `stylized_output`: anything with `.color` (1,v,3,h,w) -- two `DecoderOutput`s, or views of a `StylizedScene`.
+    One `image_io.save_images` call, i.e. one encoder call, per directory.  Returns the paths written."""
+    from .image_io import save_image, save_images
+    root = Path(output_dir) / f"{scene} | {style_image_name[:-4]}"
+    name = batch["style"]["image_name"]
+    name = name if isinstance(name, str) else name[0]
+    written = [root / name]
+    save_image(batch["style"]["image"][0], written[0])
+    ctx_index, tgt_index = batch["context"]["index"][0], batch["target"]["index"][0]
+    groups = (("context", ctx_index, batch["context"]["image"][0].detach() * 0.5 + 0.5), ("target", tgt_index, batch["target"]["image"][0]),
+              ("color", tgt_index, output.color[0]), ("stylized_color", tgt_index, stylized_output.color[0]))
+    for folder, index, frames in groups:
+        paths = [root / f"{folder}/{int(k):0>6}.png" for k in index]
+        save_images(frames.detach().float(), paths)
+        written += paths
+    return written
