@@ -626,6 +626,35 @@ int gsr_png_assemble(const void *scratch, size_t scratch_bytes, int64_t N, int H
                      int32_t *lengths, void *stream);
 
 /*
+ * JPEG frames out (csrc/gsr_jpeg_enc.hip; the reference saves its videos and .jpg pictures through ffmpeg / PIL): N pictures of one size
+ * H x W, three channels -> the entropy-coded scan of a baseline JPEG for each, ending with the EOI marker FF D9, on the device.  The bytes
+ * are libjpeg's: its integer colour conversion, box downsampling, "islow" DCT, quantisation and the Annex K Huffman tables (DESIGN.md R25
+ * states every rule).  The markers in front of the scan (SOI .. SOS) are the caller's; styl3r_amd/image_io.py jpeg_header writes them.
+ *
+ * jpeg_enc_scans: src is GSR_JPEG_ENC_SRC_U8 -- uint8 (N,H,W,3) interleaved -- or GSR_JPEG_ENC_SRC_F32_PLANAR -- fp32 (N,3,H,W), converted in
+ *     the load as (clip(x, 0, 1) * 255) truncated, NaN -> 0.  sampling is GSR_JPEG_444, GSR_JPEG_422 or GSR_JPEG_420.  quant: HOST memory,
+ *     128 values 1 .. 255, the luminance then the chrominance table in natural (row-major) order; they travel as a kernel argument.
+ *     The scan of picture n goes to out + n * out_stride (out_stride >= jpeg_enc_stream_bound), lengths[n] = its bytes (int32); bytes
+ *     beyond the length are not written.  Four launches on `stream`, no atomics on global memory, no read-back.
+ * scratch: jpeg_enc_scratch_bytes(N, H, W, sampling) of device memory, 16-byte aligned, uninitialised.  After the call it begins with the
+ *     quantised coefficients, int16 (N, blocks, 64): blocks in coding order (MCU after MCU; in an MCU the Y blocks row-major, Cb, Cr),
+ *     each in zig-zag order, entry 0 being the DC DIFFERENCE to the block of the same component before it.
+ * jpeg_enc_scratch_bytes / jpeg_enc_stream_bound return 0 for sizes the call refuses.  The bound is the worst case of the code, 22 + 63 * 26
+ * bits per block and every byte stuffed; no content or table reaches it.
+ * Returns GSR_OK; GSR_JPEG_ENC_TOO_LARGE for a picture of more than 2 500 000 blocks (nothing is launched; the caller's fallback encodes
+ * it); GSR_EINVAL before any launch: null pointers, N < 1 or > 2^24, H or W < 1 or > 65535, an unknown src_kind / sampling, a quantiser
+ * outside 1 .. 255, scratch not 16-byte aligned, fp32 src or lengths not 4-byte aligned, out_stride below the bound or above 2^31 - 1;
+ * GSR_ENOSPACE: scratch_bytes too small.
+ */
+#define GSR_JPEG_ENC_SRC_U8 0
+#define GSR_JPEG_ENC_SRC_F32_PLANAR 1
+#define GSR_JPEG_ENC_TOO_LARGE 1
+size_t gsr_jpeg_enc_scratch_bytes(int64_t N, int H, int W, int sampling);
+size_t gsr_jpeg_enc_stream_bound(int H, int W, int sampling);
+int gsr_jpeg_enc_scans(const void *src, int src_kind, int64_t N, int H, int W, int sampling, const uint16_t *quant, void *scratch,
+                       size_t scratch_bytes, uint8_t *out, size_t out_stride, int32_t *lengths, void *stream);
+
+/*
  * gsr_draw_layers (validation visuals; the reference's src/visualization/drawing/): anti-aliased lines and points drawn over B planar
  * fp32 images (B,3,H,W) on the device, `out` = `images` for in-place.  Image b carries the ordered layers image_layers[b] ..
  * image_layers[b + 1] - 1 (int32 (B + 1,)); layer l carries the records layer_prims[l] .. layer_prims[l + 1] - 1 (int32 (NL + 1,)) and is

@@ -9,7 +9,8 @@ Deviations from the reference:
     encoder to eval mode in test_step_align; nothing trains here, and the caller owns the module's mode).
   * LPIPS scores mean something only with learned weights: `scores["lpips_weights_loaded"]` says whether the module had them.
   * `test.save_image` is off by default (the reference's main.yaml turns it on): nothing is written unless the caller asks.
-Dataset loading, the evaluation index, saving videos / comparisons and logging stay with the caller.
+  * `test.save_video` writes Motion-JPEG `.avi` files (`image_io.save_video`), not the reference's `.mp4`.
+Dataset loading, the evaluation index, saving comparisons and logging stay with the caller.
 
 `estimate_relative_pose` (below) is the reference's other evaluation, `PoseEvaluator.test_step` (src/evaluation/pose_evaluator.py:48-164): the
 pose of the context views relative to the first from a PnP-RANSAC initialisation and the same alignment loop with the SSIM-structure term added.
@@ -39,6 +40,7 @@ class TestCfg:
     trans_opt_lr: float = 0.005
     compute_scores: bool = True
     save_image: bool = False                     # write the rendered target views as <output_path>/<scene>/color/<index:0>6>.png
+    save_video: bool = False                     # write them as <output_path>/video/<scene>_frame_<context indices>.avi as well
     output_path: Union[str, Path] = "outputs/test"
 
 
@@ -56,6 +58,24 @@ def save_color_images(cfg: TestCfg, batch: dict, output) -> list:
         paths = [Path(cfg.output_path) / scene / f"color/{int(k):0>6}.png" for k in index[i]]
         save_images(output.color[i].detach(), paths)
         written += paths
+    return written
+
+
+def save_color_videos(cfg: TestCfg, batch: dict, output, fps: float = 30) -> list:
+    """model_wrapper_style.py:374-379 for b >= 1 scenes: the rendered colours of scene i as one video,
+    `cfg.output_path / "video" / f"{scene}_frame_{context indices joined by _}.avi"` (`<scene>.avi` when the context carries no `index`);
+    one `image_io.save_video` call, i.e. one encoder call, per scene.  Returns the paths written."""
+    from .image_io import save_video
+    scenes = batch["scene"]
+    scenes = [scenes] if isinstance(scenes, str) else list(scenes)
+    if len(scenes) != output.color.shape[0]:
+        raise ValueError(f"save_color_videos: {len(scenes)} scene names for {output.color.shape[0]} scenes")
+    index = batch["context"].get("index")
+    written = []
+    for i, scene in enumerate(scenes):
+        name = scene if index is None else f"{scene}_frame_" + "_".join(str(int(k)) for k in index[i])
+        written.append(Path(cfg.output_path) / "video" / f"{name}.avi")
+        save_video(output.color[i].detach().float(), written[-1], fps=fps)
     return written
 
 
@@ -108,7 +128,7 @@ def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = Te
     """test_step (:317-364) for b >= 1 scenes.  Returns (DecoderOutput of the (aligned) target views, scores): scores has the reference's
     keys `psnr_ours`, `ssim_ours`, `lpips_ours` -- each the mean over a scene's target views, shape (b,) -- and `lpips_weights_loaded`;
     empty when `cfg.compute_scores` is off.  With `cfg.save_image` the rendered views are also written as PNG files (`save_color_images`;
-    `batch["scene"]` and `batch["target"]["index"]` name them)."""
+    `batch["scene"]` and `batch["target"]["index"]` name them), with `cfg.save_video` as one Motion-JPEG AVI per scene (`save_color_videos`)."""
     tgt = batch["target"]
     b, v, _, h, w = tgt["image"].shape
     style = style if style is not None else {"image": batch["context"]["image"][:, 0]}
@@ -119,6 +139,8 @@ def test_step(encoder, decoder, batch: dict, losses: Sequence, cfg: TestCfg = Te
         output = decoder.forward(gaussians, extrinsics, tgt["intrinsics"], tgt["near"], tgt["far"], (h, w))
     if cfg.save_image:
         save_color_images(cfg, batch, output)
+    if cfg.save_video:
+        save_color_videos(cfg, batch, output)
     if not cfg.compute_scores:
         return output, {}
     gt, pred = tgt["image"].reshape(b * v, -1, h, w), output.color.reshape(b * v, -1, h, w)

@@ -1,4 +1,5 @@
-"""Writing pictures: the reference's src/misc/image_io.py (`prep_image`, `save_image`, `load_image`) with the PNG encoder on the device.
+"""Writing pictures and videos: the reference's src/misc/image_io.py (`prep_image`, `save_image`, `load_image`, `save_video`) with the PNG
+and the baseline-JPEG encoder on the device.
 
 `encode_png` turns N frames of one size into N complete PNG files.  Device tensors go through csrc/gsr_png.hip: `gsr_png_chunks` (one
 workgroup per chunk of whole rows: filter, byte-run tokens, Huffman code, dynamic deflate block) and `gsr_png_assemble` (the zlib stream
@@ -11,6 +12,11 @@ The stream of one image: `78 01`, then per chunk either one dyna
 `01 00 00 FF FF` and the Adler-32 of the filtered bytes.  A chunk is the largest number of whole rows whose filtered bytes
 rows * (1 + W * C) fit GSR_PNG_CHUNK_BYTES; an image whose single row does not fit goes to Pillow and is counted in
 CALLS["png_fallback"].  Only 8-bit RGB / RGBA, no interlace, no ancillary chunks.
+
+`encode_jpeg` turns N frames of one size into N baseline JPEG files that are Pillow's (libjpeg's) bytes: csrc/gsr_jpeg_enc.hip writes the
+entropy-coded scans, `jpeg_header` the markers in front of them.  CPU tensors go to Pillow itself.  `save_video` puts the
+files of one `encode_jpeg` call into a Motion-JPEG AVI (the reference writes H.264 .mp4 through ffmpeg, which this build does not have);
+`read_avi` is its inverse.
 """
 from __future__ import annotations
 
@@ -28,7 +34,8 @@ from torch import Tensor
 from . import _lib
 from ._lib import GSR_PNG_CHUNK_BYTES as CHUNK_BYTES
 
-CALLS = {"png_hip": 0, "png_host": 0, "png_fallback": 0}     # images encoded on the device / by the restatement / by Pillow
+# images encoded on the device / by the restatement / by Pillow; JPEG: on the device / by Pillow for CPU tensors / by Pillow for a refused size
+CALLS = {"png_hip": 0, "png_host": 0, "png_fallback": 0, "jpeg_enc_hip": 0, "jpeg_enc_host": 0, "jpeg_enc_fallback": 0}
 DEBUG_FILL: Optional[int] = None    # tests: a byte value the device buffers are filled with before the launches (an unwritten byte shows)
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 FILTERS = {"adaptive": 0, "none": 1}
@@ -68,10 +75,17 @@ def load_image(path) -> Tensor:
 
 
 def save_image(image: Tensor, path) -> None:
-    """image_io.py:57-68: save an image in range 0-1, the parent directory created.  A `.png` path takes `encode_png`; any other
-    suffix goes to Pillow (the drivers save the style image under its own name, often .jpg)."""
+    """image_io.py:57-68: save an image in range 0-1, the parent directory created.  A `.png` path takes `encode_png`; a `.jpg` / `.jpeg`
+    path with a three-channel device tensor takes `encode_jpeg` at Pillow's defaults (quality 75, 4:2:0), so the file is the one Pillow
+    writes; any other suffix, and CPU tensors under .jpg, go to Pillow (the drivers save the style image under its own name, often .jpg)."""
     path = Path(path)
     path.parent.mkdir(exist_ok=True, parents=True)
+    if path.suffix.lower() in (".jpg", ".jpeg") and image.is_cuda:
+        planar = image.ndim == 3 and image.shape[0] == 3 and image.dtype == torch.float32
+        frames = image.detach()[None] if planar else prep_image(image)[None]
+        if planar or frames.shape[-1] == 3:                      # (four channels: Pillow refuses them below, as it always did)
+            path.write_bytes(encode_jpeg(frames, quality=75, subsampling="4:2:0")[0])
+            return
     if path.suffix.lower() != ".png":
         from PIL import Image
         Image.fromarray(prep_image(image).cpu().numpy()).save(path)
@@ -450,3 +464,203 @@ def encode_png(frames: Tensor, filter: str = "adaptive", details: Optional[dict]
     used = out.view(N, stride)[:, :max(sizes)].cpu().numpy()    # read-back 2
     CALLS["png_hip"] += N
     return [wrap_png(used[i, :n].tobytes(), H, W, ch) for i, n in enumerate(sizes)]
+
+
+# ---- baseline JPEG ---------------------------------------------------------------------------------------------------------------------
+JPEG_SAMPLING = {"4:4:4": (_lib.GSR_JPEG_444, 1, 1, 0), "4:2:2": (_lib.GSR_JPEG_422, 2, 1, 1), "4:2:0": (_lib.GSR_JPEG_420, 2, 2, 2)}   # library's code, Y factors, Pillow's number
+ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
+          57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63)
+QUANT_BASE = (      # ITU-T T.81 Annex K tables K.1 (luminance) and K.2 (chrominance), row-major
+    (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+     18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99),
+    (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99)
+    + (99,) * 32)
+HUFF_BITS = {   # Annex K tables K.3 - K.6: codes per length 1 .. 16, keyed (class: 0 DC / 1 AC, table: 0 luminance / 1 chrominance)
+    (0, 0): (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0), (1, 0): (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125),
+    (0, 1): (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0), (1, 1): (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119)}
+HUFF_VALS = {
+    (0, 0): tuple(range(12)), (0, 1): tuple(range(12)),
+    (1, 0): (1, 2, 3, 0, 4, 17, 5, 18, 33, 49, 65, 6, 19, 81, 97, 7, 34, 113, 20, 50, 129, 145, 161, 8, 35, 66, 177, 193, 21, 82, 209, 240, 36, 51,
+             98, 114, 130, 9, 10, 22, 23, 24, 25, 26, 37, 38, 39, 40, 41, 42, 52, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74, 83, 84,
+             85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 131, 132, 133, 134, 135, 136,
+             137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180, 181, 182, 183,
+             184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 225, 226, 227, 228, 229,
+             230, 231, 232, 233, 234, 241, 242, 243, 244, 245, 246, 247, 248, 249, 250),
+    (1, 1): (0, 1, 2, 3, 17, 4, 5, 33, 49, 6, 18, 65, 81, 7, 97, 113, 19, 34, 50, 129, 8, 20, 66, 145, 161, 177, 193, 9, 35, 51, 82, 240, 21, 98,
+             114, 209, 10, 22, 36, 52, 225, 37, 241, 23, 24, 25, 26, 38, 39, 40, 41, 42, 53, 54, 55, 56, 57, 58, 67, 68, 69, 70, 71, 72, 73, 74,
+             83, 84, 85, 86, 87, 88, 89, 90, 99, 100, 101, 102, 103, 104, 105, 106, 115, 116, 117, 118, 119, 120, 121, 122, 130, 131, 132, 133,
+             134, 135, 136, 137, 138, 146, 147, 148, 149, 150, 151, 152, 153, 154, 162, 163, 164, 165, 166, 167, 168, 169, 170, 178, 179, 180,
+             181, 182, 183, 184, 185, 186, 194, 195, 196, 197, 198, 199, 200, 201, 202, 210, 211, 212, 213, 214, 215, 216, 217, 218, 226, 227,
+             228, 229, 230, 231, 232, 233, 234, 242, 243, 244, 245, 246, 247, 248, 249, 250)}
+AVIF_HASINDEX, AVIIF_KEYFRAME = 0x10, 0x10
+JPEG_BATCH_BYTES = 1 << 31          # encode_jpeg: most device memory (scratch + worst-case output) of one library call; more frames go in batches
+AVI_LIMIT = 1 << 31                 # AVI 1.0: one RIFF chunk; OpenDML is not written
+
+
+def _jpeg_args(quality, subsampling, who: str):
+    if isinstance(quality, bool) or not isinstance(quality, int) or not 1 <= quality <= 100:
+        raise ValueError(f"{who}: quality is an integer in 1 .. 100, not {quality!r}")
+    if subsampling not in JPEG_SAMPLING:
+        raise ValueError(f"{who}: subsampling is '4:4:4', '4:2:2' or '4:2:0', not {subsampling!r}")
+
+
+def jpeg_quant_tables(quality: int) -> np.ndarray:
+    """libjpeg's jpeg_set_quality: uint16 (2, 64), luminance and chrominance in natural order.  scale = 5000 / quality below 50, else
+    200 - 2 quality; an entry is (base * scale + 50) / 100 in integers, clamped to 1 .. 255."""
+    scale = 5000 // quality if quality < 50 else 200 - 2 * quality
+    return np.clip((np.array(QUANT_BASE, np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16)
+
+
+def jpeg_header(H: int, W: int, quality: int = 90, subsampling: str = "4:2:0") -> bytes:
+    """Everything a baseline JPEG file holds in front of its scan, as Pillow / libjpeg write it: SOI, APP0 (JFIF 1.1, no units, density
+    1 x 1, no thumbnail), the two quantisation tables (8-bit, zig-zag), SOF0 (components 1, 2, 3; tables 0, 1, 1), the four Annex K
+    Huffman tables in the order DC0, AC0, DC1, AC1, and SOS (Ss 0, Se 63, Ah / Al 0)."""
+    _jpeg_args(quality, subsampling, "jpeg_header")
+    if not (1 <= H <= 65535 and 1 <= W <= 65535):
+        raise ValueError(f"jpeg_header: a JPEG picture is 1 .. 65535 pixels on a side, not {H} x {W}")
+    _, hs, vs, _ = JPEG_SAMPLING[subsampling]
+    seg = lambda marker, data: bytes((0xFF, marker)) + struct.pack(">H", len(data) + 2) + data
+    out = b"\xff\xd8" + seg(0xE0, b"JFIF\x00\x01\x01\x00" + struct.pack(">HHBB", 1, 1, 0, 0))
+    for t, table in enumerate(jpeg_quant_tables(quality)):
+        out += seg(0xDB, bytes((t,)) + bytes(int(table[ZIGZAG[k]]) for k in range(64)))
+    out += seg(0xC0, struct.pack(">BHHB", 8, H, W, 3) + bytes((1, hs << 4 | vs, 0, 2, 0x11, 1, 3, 0x11, 1)))
+    for table in (0, 1):
+        for cls in (0, 1):
+            out += seg(0xC4, bytes((cls << 4 | table,)) + bytes(HUFF_BITS[cls, table]) + bytes(HUFF_VALS[cls, table]))
+    return out + seg(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+
+
+def _pillow_jpeg(frames: np.ndarray, quality: int, subsampling: str) -> list:
+    from PIL import Image
+    out = []
+    for img in frames:
+        buf = BytesIO()
+        Image.fromarray(img).save(buf, format="JPEG", quality=quality, subsampling=JPEG_SAMPLING[subsampling][3])
+        out.append(buf.getvalue())
+    return out
+
+
+def encode_jpeg(frames: Tensor, quality: int = 90, subsampling: str = "4:2:0") -> list:
+    """N frames of one size -> N baseline JPEG files as bytes, the ones Pillow's `save(format="JPEG", quality=, subsampling=)` writes.
+    `frames`: uint8 (N,H,W,3) or fp32 (N,3,H,W); fp32 values are converted as `prep_image` does, in the kernel's load.  Device tensors
+    take the kernels -- four launches and two read-backs (the scan lengths, then the used bytes) for as many frames as fit
+    JPEG_BATCH_BYTES of scratch and worst-case output, 58 frames of 1080 x 1920 or 1 800 of 256 x 256 at 4:2:0 -- and raise if the
+    library is missing; CPU tensors take Pillow.  A picture the kernels refuse (more than 2.5 million blocks) goes to Pillow and is
+    counted in CALLS["jpeg_enc_fallback"]."""
+    _jpeg_args(quality, subsampling, "encode_jpeg")
+    if not isinstance(frames, Tensor) or frames.ndim != 4 or frames.dtype not in (torch.uint8, torch.float32):
+        raise ValueError("encode_jpeg takes uint8 (N,H,W,3) or float32 (N,3,H,W) frames")
+    planar = frames.dtype == torch.float32
+    N, (H, W, ch) = frames.shape[0], ((frames.shape[2], frames.shape[3], frames.shape[1]) if planar else frames.shape[1:])
+    if ch != 3 or N < 1 or H < 1 or W < 1:
+        raise ValueError(f"encode_jpeg: {N} frames of {H} x {W} with {ch} channels; frames are RGB and not empty")
+    frames = frames.detach().contiguous()
+    if not frames.is_cuda:
+        CALLS["jpeg_enc_host"] += N
+        return _pillow_jpeg(_bytes_host(frames), quality, subsampling)
+    lib, dev, code = _lib.load(), frames.device, JPEG_SAMPLING[subsampling][0]
+    bound = lib.gsr_jpeg_enc_stream_bound(H, W, code)
+    if not bound or not lib.gsr_jpeg_enc_scratch_bytes(1, H, W, code):
+        CALLS["jpeg_enc_fallback"] += N
+        return _pillow_jpeg(_bytes_host(frames), quality, subsampling)
+    stride = (bound + 15) & ~15
+    per = max(1, JPEG_BATCH_BYTES // (stride + lib.gsr_jpeg_enc_scratch_bytes(1, H, W, code)))      # frames per library call
+    make = (lambda n: torch.empty(n, dtype=torch.uint8, device=dev)) if DEBUG_FILL is None else \
+        (lambda n: torch.full((n,), DEBUG_FILL, dtype=torch.uint8, device=dev))
+    quant = np.ascontiguousarray(jpeg_quant_tables(quality))
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    header, files = jpeg_header(H, W, quality, subsampling), []
+    for at in range(0, N, per):
+        part = frames[at:at + per]
+        n = part.shape[0]
+        nbytes = lib.gsr_jpeg_enc_scratch_bytes(n, H, W, code)
+        scratch, out, lengths = make(nbytes), make(n * stride), make(4 * n).view(torch.int32)
+        _lib.check(lib.gsr_jpeg_enc_scans(part.data_ptr(), _lib.GSR_JPEG_ENC_SRC_F32_PLANAR if planar else _lib.GSR_JPEG_ENC_SRC_U8, n, H, W, code,
+                                          quant.ctypes.data, scratch.data_ptr(), nbytes, out.data_ptr(), stride, lengths.data_ptr(), stream),
+                   "gsr_jpeg_enc_scans")
+        sizes = lengths.cpu().tolist()                              # read-back 1
+        if min(sizes) < 2 or max(sizes) > bound:
+            raise RuntimeError(f"encode_jpeg: scan lengths {min(sizes)} .. {max(sizes)} outside [2, {bound}]")
+        used = out.view(n, stride)[:, :max(sizes)].cpu().numpy()    # read-back 2
+        files += [header + used[i, :k].tobytes() for i, k in enumerate(sizes)]
+    CALLS["jpeg_enc_hip"] += N
+    return files
+
+
+# ---- Motion-JPEG AVI -------------------------------------------------------------------------------------------------------------------
+def _riff(kind: bytes, data: bytes) -> bytes:
+    return kind + struct.pack("<I", len(data)) + data + b"\x00" * (len(data) & 1)
+
+
+def wrap_avi(files: Sequence, H: int, W: int, fps: float) -> bytes:
+    """JPEG files of one size -> an AVI 1.0 file: RIFF AVI, LIST hdrl (avih with AVIF_HASINDEX; one LIST strl: strh vids / MJPG with
+    dwRate / dwScale = fps, scale 1 for an integer fps and 1000 otherwise; strf: a 40-byte BITMAPINFOHEADER, MJPG, 24 bits, 1 plane),
+    LIST movi of `00dc` chunks padded to even length, idx1 (every frame a key frame, offsets from the `movi` fourcc)."""
+    if not fps > 0:
+        raise ValueError(f"save_video: fps is positive, not {fps!r}")
+    scale = 1 if float(fps).is_integer() else 1000
+    rate, n = int(round(fps * scale)), len(files)
+    largest = max((len(f) for f in files), default=0)
+    total = 12 + (12 + 64 + 12 + 64 + 48) + 12 + sum(8 + len(f) + (len(f) & 1) for f in files) + 8 + 16 * n
+    if total >= AVI_LIMIT:
+        raise ValueError(f"save_video: the file would hold {total} bytes; this build writes AVI 1.0, below 2 GiB -- save fewer frames per file")
+    avih = struct.pack("<14I", int(round(1e6 * scale / rate)), 0, 0, AVIF_HASINDEX, n, 0, 1, largest, W, H, 0, 0, 0, 0)
+    strh = b"vidsMJPG" + struct.pack("<IHHIIIIIIiI4h", 0, 0, 0, 0, scale, rate, 0, n, largest, -1, 0, 0, 0, W, H)
+    strf = struct.pack("<IiiHH4sIiiII", 40, W, H, 1, 24, b"MJPG", W * H * 3, 0, 0, 0, 0)
+    hdrl = b"hdrl" + _riff(b"avih", avih) + _riff(b"LIST", b"strl" + _riff(b"strh", strh) + _riff(b"strf", strf))
+    movi, index, at = [b"movi"], [], 4
+    for f in files:
+        index.append(struct.pack("<4sIII", b"00dc", AVIIF_KEYFRAME, at, len(f)))
+        movi.append(_riff(b"00dc", f))
+        at += len(movi[-1])
+    body = b"AVI " + _riff(b"LIST", hdrl) + _riff(b"LIST", b"".join(movi)) + _riff(b"idx1", b"".join(index))
+    out = _riff(b"RIFF", body)
+    assert len(out) == total, (len(out), total)
+    return out
+
+
+def save_video(images, path, fps: float = 30, quality: int = 90, subsampling: str = "4:2:0") -> None:
+    """image_io.py's save_video: the frames as a video file, the parent directory created.  `images`: the reference's list of fp32
+    (3,H,W) images in 0 .. 1, an fp32 (F,3,H,W) tensor, or the uint8 (F,H,W,3) tensor `inference.render_flythrough` returns.  One
+    `encode_jpeg` call for all frames.  The file is Motion-JPEG in an AVI container, so the suffix must be `.avi` (the reference writes
+    H.264 into .mp4 through ffmpeg)."""
+    path = Path(path)
+    if path.suffix.lower() != ".avi":
+        raise ValueError(f"save_video: this build writes Motion-JPEG AVI; name the file .avi, not {path.name!r}")
+    if not isinstance(images, Tensor):
+        images = list(images)
+        if not images or any(not isinstance(i, Tensor) or i.ndim != 3 for i in images):
+            raise ValueError("save_video takes a non-empty list of (3,H,W) images, an (F,3,H,W) tensor or a uint8 (F,H,W,3) tensor")
+        images = torch.stack([i.detach().float() for i in images])
+    files = encode_jpeg(images, quality, subsampling)
+    H, W = (images.shape[2], images.shape[3]) if images.dtype == torch.float32 else (images.shape[1], images.shape[2])
+    data = wrap_avi(files, H, W, fps)
+    path.parent.mkdir(exist_ok=True, parents=True)
+    path.write_bytes(data)
+
+
+def read_avi(path) -> tuple:
+    """(fps, [the JPEG file of every frame]) of a Motion-JPEG AVI as `save_video` writes it: the `00dc` chunks of LIST movi in order,
+    fps = dwRate / dwScale of the stream header"""
+    data = Path(path).read_bytes()
+    if data[:4] != b"RIFF" or data[8:12] != b"AVI ":
+        raise ValueError(f"read_avi: {path} is not a RIFF AVI file")
+    fps, frames = None, []
+
+    def walk(at: int, end: int):
+        nonlocal fps
+        while at + 8 <= end:
+            kind, n = data[at:at + 4], struct.unpack("<I", data[at + 4:at + 8])[0]
+            if kind == b"LIST":
+                if data[at + 8:at + 12] in (b"hdrl", b"strl", b"movi"):
+                    walk(at + 12, at + 8 + n)
+            elif kind == b"strh" and data[at + 8:at + 12] == b"vids":
+                scale, rate = struct.unpack("<II", data[at + 28:at + 36])
+                fps = rate / scale
+            elif kind == b"00dc":
+                frames.append(data[at + 8:at + 8 + n])
+            at += 8 + n + (n & 1)
+    walk(12, min(len(data), 8 + struct.unpack("<I", data[4:8])[0]))
+    if fps is None:
+        raise ValueError(f"read_avi: {path} has no video stream header")
+    return fps, frames

@@ -196,6 +196,19 @@ def render_flythrough(decoder, scene_or_gaussians: Union[StylizedScene, Gaussian
     return pack_frames(tensors, axis=axis, gap=gap, loop_reverse=KINDS[kind][2] if loop_reverse is None else loop_reverse, depth_range=rng)
 
 
+def save_flythrough(path, decoder, scene_or_gaussians, context: dict, *, fps: float = 30, quality: int = 90, **render) -> Tensor:
+    """`render_video_generic` of the inference drivers: `render_flythrough(decoder, scene_or_gaussians, context, **render)` followed by
+    `image_io.save_video(frames, path, fps, quality)`.  The frames stay on the device between the two -- the JPEG encoder reads the
+    uint8 tensor `pack_frames` wrote -- and only the coded bytes come to the host.  `path` ends in `.avi` (Motion-JPEG; the reference
+    writes .mp4).  Returns the frames."""
+    from .image_io import save_video
+    if Path(path).suffix.lower() != ".avi":
+        raise ValueError(f"save_flythrough: this build writes Motion-JPEG AVI; name the file .avi, not {Path(path).name!r}")
+    frames = render_flythrough(decoder, scene_or_gaussians, context, **render)
+    save_video(frames, path, fps=fps, quality=quality)
+    return frames
+
+
 def export_scene_ply(scene: StylizedScene, directory, shift_and_scale: bool = False, save_sh_dc_only: bool = True) -> list:
     """infer_model_re10k.py:542-557: `gaussians.ply` for the un-stylized set and `stylized_gaussians.ply` for the stylized one
     (`stylized_gaussians_<s>.ply` per style when the scene holds several), scales and rotations from the visualization dump.
