@@ -123,14 +123,15 @@ __global__ void __launch_bounds__(256) k_adapter_bwd(VitAdapterArgs a, const flo
     float *gp = const_cast<float *>(sample_ptr(d_pts0, d_ptsr, bi, view, a.v, 3, HW)) + r;
     float *ga = const_cast<float *>(sample_ptr(d_par0, d_parr, bi, view, a.v, a.par_channels, HW)) + r;
 
-    // ---- means: m = xyz * (f / d)  (d >= 1e-8; below it the direction is xyz * 1e8 and f ~ d: the same expression holds to O(d)) ----
+    // ---- means: m = xyz * (f / dn), dn = max(d, 1e-8): dm_c/dxyz_a = delta_ca f / dn + xyz_c xyz_a coef ----
     {
         const float dn = fmaxf(g.d, 1e-8f);
         const float gm[3] = {d_means[idx * 3], d_means[idx * 3 + 1], d_means[idx * 3 + 2]};
         const float ratio = g.f / dn;
         const float dot = gm[0] * g.xyz[0] + gm[1] * g.xyz[1] + gm[2] * g.xyz[2];
-        // d(f/d)/dxyz = ((f' d - f) / d^2) * xyz / d, f' = exp(d) = f + 1
-        const float coef = (g.d >= 1e-8f) ? (((g.f + 1.0f) * dn - g.f) / (dn * dn)) / dn : 0.0f;
+        // d >= 1e-8: d(f/d)/dxyz = ((f' d - f) / d^2) * xyz / d, f' = exp(d) = f + 1.  0 < d < 1e-8: the clip holds dn at 1e-8 and only f
+        // varies, d(f/dn)/dxyz = (f' / dn) * xyz / d -- as large as the first term (f ~ d).  d = 0: |xyz| has the subgradient 0 there.
+        const float coef = (g.d >= 1e-8f) ? (((g.f + 1.0f) * dn - g.f) / (dn * dn)) / dn : (g.d > 0.0f) ? (g.f + 1.0f) / (dn * g.d) : 0.0f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) gp[c * HW] = gm[c] * ratio + g.xyz[c] * (dot * coef);
     }
