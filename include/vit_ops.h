@@ -406,6 +406,33 @@ typedef struct VitAdamChunk {
 int vit_adamw_step(const VitAdamChunk *chunks, int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay,
                    const float *grad_scale, void *stream);
 
+/* ---- checkpoint snapshot (vit_snapshot.hip): the whole training state leaves the train stream in ONE launch ----
+ * chunks: device array, one workgroup each; chunk i = nbytes (at most the chunk size, all of ONE tensor) at src, copied exactly to
+ * staging + dst_off.  Tensor starts in `staging` are multiples of 64 bytes and the chunks of a tensor follow each other at multiples of the
+ * chunk size, so dst_off is always 16-byte aligned; the bytes between two tensors are not written.  flags: VIT_SNAP_FP32 -- count the words
+ * whose fp32 exponent field is all ones; VIT_SNAP_VEC16 / VIT_SNAP_WORD promise a 16- / 4-byte aligned src (neither: byte loads).
+ * partials[i] (device, 8-byte aligned): s1 = sum w_j, s2 = sum (j + 1) w_j mod 2^64 over the chunk's little-endian 32-bit words, j local to the
+ * chunk, a final partial word zero-extended.  A tensor's checksum is S1 = sum s1_c, S2 = sum (s2_c + base_c s1_c) mod 2^64 with base_c the word
+ * index of chunk c's start in the tensor (styl3r_amd/checkpointing.py folds it and restates it in numpy).  Integer sums, no atomics: bit-identical
+ * from run to run.  The table is trusted: the caller sizes `staging` for every dst_off + nbytes. */
+#define VIT_SNAP_FP32 1
+#define VIT_SNAP_VEC16 2
+#define VIT_SNAP_WORD 4
+typedef struct VitSnapChunk {
+    const void *src;
+    uint64_t dst_off;
+    uint32_t nbytes;
+    uint32_t flags;
+} VitSnapChunk;
+typedef struct VitSnapPartial {
+    uint64_t s1;
+    uint64_t s2;
+    uint32_t nonfinite;
+    uint32_t reserved;
+} VitSnapPartial;
+size_t vit_snapshot_chunk_bytes(void);
+int vit_snapshot_pack(const VitSnapChunk *chunks, int n_chunks, void *staging, VitSnapPartial *partials, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

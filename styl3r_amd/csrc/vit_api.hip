@@ -48,6 +48,8 @@ int linear_x6c_fwd(const float *x, const void *wp, const float *bias, const floa
                    int act, int splits, void *workspace, size_t workspace_bytes, hipStream_t stream);
 int adamw_step(const VitAdamChunk *chunks, int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay,
                const float *grad_scale, hipStream_t stream);
+size_t snapshot_chunk_bytes();
+int snapshot_pack(const VitSnapChunk *chunks, int n_chunks, void *staging, VitSnapPartial *partials, hipStream_t stream);
 int x6_set_products(int n);
 int x6_products();
 int x6_set_operand_amax(const void *a, const void *b);
@@ -125,6 +127,11 @@ VIT_EXPORT int vit_adamw_step(const VitAdamChunk *chunks, int n_chunks, float lr
                               const float *grad_scale, void *stream)
 {
     return vit::adamw_step(chunks, n_chunks, lr, beta1, beta2, eps, weight_decay, grad_scale, static_cast<hipStream_t>(stream));
+}
+VIT_EXPORT size_t vit_snapshot_chunk_bytes(void) { return vit::snapshot_chunk_bytes(); }
+VIT_EXPORT int vit_snapshot_pack(const VitSnapChunk *chunks, int n_chunks, void *staging, VitSnapPartial *partials, void *stream)
+{
+    return vit::snapshot_pack(chunks, n_chunks, staging, partials, static_cast<hipStream_t>(stream));
 }
 VIT_EXPORT int vit_x6_set_products(int n) { return vit::x6_set_products(n); }
 VIT_EXPORT int vit_x6_products(void) { return vit::x6_products(); }

@@ -159,6 +159,40 @@ class TrainStep:
         self._weights = [p for p in encoder.parameters() if id(p) in trainable and p.dim() == 2]
         self.global_step = 0
 
+    def state_dict(self, optimizer: bool = True) -> dict:
+        """{"encoder": every weight and buffer of the encoder (frozen ones included), "optimizer": `optimizer.state_dict()`, "scheduler": the
+        scheduler's or None, "global_step": n} -- references to the live tensors, not copies (checkpointing.snapshot takes the copy).
+        COLLECTIVE in "rs_ag" mode on more than one rank: it fences the parameter all-gather (`reducer.wait_params()`) and, unless
+        `optimizer=False` (a weights-only save: "optimizer" and "scheduler" are then None), all-gathers the moment shards
+        (`reducer.consolidate_optimizer_state`), so every rank has to call it."""
+        self.reducer.wait_params()
+        sd = {"encoder": {k: v.detach() for k, v in self.encoder.state_dict().items()}, "optimizer": None, "scheduler": None,
+              "global_step": int(self.global_step)}
+        if optimizer:
+            if self.dp_mode == "rs_ag":
+                self.reducer.consolidate_optimizer_state(self.optimizer)
+            sd["optimizer"] = self.optimizer.state_dict()
+            sd["scheduler"] = self.scheduler.state_dict() if self.scheduler is not None else None
+        return sd
+
+    def load_state_dict(self, sd: dict):
+        """The inverse of `state_dict()`; entries that are missing or None are left as they are (a weights-only checkpoint restores the
+        encoder and nothing else).  The encoder's tensors are overwritten IN PLACE (`Tensor.copy_` bumps their version counters, so
+        vit_ops' pre-split weight images and the |max| words published for them are not served for the old values; the reducer's bucket
+        views and the optimizer's parameter references stay valid), the optimizer drops its chunk tables with its replaced moments
+        (`AdamWHIP.load_state_dict`).  In "rs_ag" mode every rank loads the full moments and goes on updating its owned ranges."""
+        self.reducer.wait_params()
+        if sd.get("encoder") is not None:
+            self.encoder.load_state_dict(sd["encoder"], strict=True)
+        if sd.get("optimizer") is not None:
+            self.optimizer.load_state_dict(sd["optimizer"])
+        if sd.get("scheduler") is not None:
+            if self.scheduler is None:
+                raise ValueError("TrainStep.load_state_dict: the state has a scheduler, this TrainStep was built without warm_up_steps")
+            self.scheduler.load_state_dict(sd["scheduler"])
+        if sd.get("global_step") is not None:
+            self.global_step = int(sd["global_step"])
+
     def _encode(self, ctx, style, dump=None, **kw):
         if dump is not None:
             kw["visualization_dump"] = dump
