@@ -11,7 +11,8 @@ Mirrors the reference operator interfaces:
     -> `fused_linear`: vit_linear_x6_fwd (fp32-accurate bf16x6, default) or vit_linear_fwd (exact-f32 MFMA), dX on the
        pre-split transposed weight, dW + db on vit_linear_x6_wgrad (accumulating into all-reduce bucket slices);
        VIT_LINEAR_MODE=bf16x3: three instead of six partial products per launch (~4e-6 per GEMM; third pieces neither computed nor staged);
-       large-M shapes go to the LDS-DMA ring kernels (vit_linear_x6r_fwd, `_RING_SHAPES`); `GeluLink`: GELU' in fc2's dX epilogue
+       `_linear_cfg` is the ONE route (which kernel and weight image a shape takes: forward, dX, serving; LDS-DMA rings `_RING_SHAPES`, small-M /
+       narrow-N kernel) and `_launch_linear` the ONE x6 launch (image, |max| words, entry point); `GeluLink`: GELU' in fc2's dX epilogue
   * `nn.LayerNorm(eps=1e-6)`, blocks.py:144-152,205-222                                        -> `LayerNorm` (vit_layernorm_*)
   * `nn.Conv2d` 3x3 / 1x1 stride 1 of the DPT heads and VGG, dpt_block.py:79-218,350-419      -> `Conv2dX6` (vit_conv_x6_*; small 3x3 dW:
     vit_im2col3_rows + vit_linear_x6_wgrad)
@@ -878,9 +879,9 @@ def linear_x6r(x: Tensor, packed_block: Tensor, N: int, bias: Optional[Tensor] =
     M = x2.shape[0]
     out = torch.empty(M, N, dtype=torch.float32, device=x.device)
     res = residual.reshape(M, N).contiguous().float() if residual is not None else None
-    _check(load().vit_linear_x6r_fwd(x2.data_ptr(), packed_block.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                     res.data_ptr() if res is not None else None, out.data_ptr(), None, M, N, K, 1 if gelu else 0,
-                                     cfg, _stream(x.device)), "vit_linear_x6r_fwd")
+    if cfg == 0:
+        raise ValueError("linear_x6r: cfg 0 is vit_linear_x6_fwd on the row image, not a ring configuration")
+    _launch_linear(x2, None, out, M, N, K, cfg, image=packed_block, bias=bias, residual=res, act=1 if gelu else 0, count=None)
     return out.reshape(*x.shape[:-1], N)
 
 
@@ -1498,11 +1499,29 @@ _RING_SHAPES_MID = {"f16x3": {(2304, 768): 1, (3072, 768): 1, (4096, 1024): 3, (
 RING_DISPATCH = os.environ.get("VIT_RING_DISPATCH", "1") == "1"
 
 
-def _ring_cfg(M: int, N: int, K: int) -> int:
-    # csrc/vit_gemm_sm.hip in the AUTOGRAD path: narrow outputs at train-step row counts.  (At M <= SMALL_M_ROWS it serves the no-grad path only --
-    # `fused_linear` asks `small_m_kernel` itself: nothing trains at 257 / 514 rows except the parity fixtures, and those were recorded against the
-    # summation order of the 128-row kernels: with the small-M kernel in their forward the c3 fixture's style-encoder gradients sit in the
-    # flip-prone state of DESIGN 9 (3) in EVERY run instead of two runs in five -- profiles/r06_c3_stylizer_rows_ab.txt)
+def _linear_cfg(M: int, N: int, K: int, *, dx: bool = False, serving: bool = False, mode: Optional[str] = None) -> int:
+    """THE route of a fused-Linear launch of a layer (N, K) at M rows: 0 = vit_linear_x6_fwd on the ROW image; 1 / 3 (LDS-DMA rings) and 5
+    (csrc/vit_gemm_sm.hip) = vit_linear_x6r_fwd on the BLOCK image -- `cfg != 0` is the layout of the image, for the launch, the staleness probe
+    and the pair split alike.  "f32" has no x6 launch: 0.
+    serving (no grad): the small-M kernel where `small_m_kernel` takes the shape, else 0 -- at EVERY row count, above 2048 too: the serving path
+      takes neither the rings nor the narrow-output route (batch-1 serving runs at 257 / 514 rows; larger no-grad launches were never A/B-ed).
+    training forward: the narrow-output kernel (5) above SMALL_M_ROWS, else the ring table of the row count (>= 4096 / >= 2048), else 0.
+    dx: the input-gradient GEMM (dX = dY . W: the forward rule with N and K exchanged) -- ring kernels in three-product mode only (in six-product
+      mode the A/B on the whole step lost 3 ms), the narrow-output kernel in every mode; `mode`: the mode of the node's forward -- once LINEAR_MODE
+      has moved on, the row image."""
+    if LINEAR_MODE == "f32":
+        return 0
+    if serving:
+        return 5 if small_m_kernel(M, N, K) else 0
+    if dx:
+        if mode is not None and mode != LINEAR_MODE:
+            return 0
+        cfg = _linear_cfg(M, K, N)
+        return cfg if (cfg == 5 or LINEAR_MODE in ("bf16x3", "f16x3")) else 0
+    # csrc/vit_gemm_sm.hip in the AUTOGRAD path: narrow outputs at train-step row counts only.  (Nothing trains at 257 / 514 rows except the parity
+    # fixtures, and those were recorded against the summation order of the 128-row kernels: with the small-M kernel in their forward the c3
+    # fixture's style-encoder gradients sit in the flip-prone state of DESIGN 9 (3) in EVERY run instead of two runs in five --
+    # profiles/r06_c3_stylizer_rows_ab.txt)
     # (tried and dropped: every served shape at 1 024 < M < 2 048 -- the C4 style stage's 1 536-row style encoder, whose 1024-wide layers are
     #  split-contraction launches of the 128-row kernel.  The kernel lab says -9 .. -40 % per launch there, the C4 step says 374.6 -> 378.8 / 384.5 ms:
     #  profiles/r06_mid_rows_ab.jsonl, profiles/r06_small_linear_lab_m1536.txt)
@@ -1513,11 +1532,31 @@ def _ring_cfg(M: int, N: int, K: int) -> int:
     return (_RING_SHAPES if M >= 4096 else _RING_SHAPES_MID).get(LINEAR_MODE, {}).get((N, K), 0)
 
 
-def _ring_cfg_dx(M: int, N: int, K: int) -> int:
-    """... of the input-gradient GEMM of a Linear (N, K), for the forward (which image a pair split builds) and the backward (which kernel reads it):
-    ring kernels in three-product mode only (in six-product mode the A/B on the whole step lost 3 ms), the narrow-output kernel (5) in every mode"""
-    ring = _ring_cfg(M, K, N)
-    return ring if (ring == 5 or LINEAR_MODE in ("bf16x3", "f16x3")) else 0
+def _launch_linear(a2: Tensor, weight: Optional[Tensor], out: Tensor, M: int, N: int, K: int, cfg: int, *, image: Optional[Tensor] = None, transposed: bool = False,
+                   bias: Optional[Tensor] = None, residual: Optional[Tensor] = None, pre: Optional[Tensor] = None, act: int = 0,
+                   operand_word: Optional[Tensor] = None, want_word: bool = False, count: Optional[str] = "linear_x6r", what: str = "") -> Optional[Tensor]:
+    """THE x6 launch of a Linear: out (M, N) = [residual +] act(a2 (M, K) . W^T + bias), M / N / K as the kernel sees them, on the kernel of `cfg`
+    (`_linear_cfg`) and the image that kernel reads, in the order the library's per-thread |max| words need (f16x3): the weight image FIRST
+    (a lazy split announces and consumes the weight's word itself), then the activation's `operand_word` (None outside f16x3), then --
+    `want_word` -- a zeroed word for the |max| of what the epilogue stores (returned: the caller links or publishes it), then the launch.
+    transposed: the input-gradient GEMM (a2 = dY, out = dX, residual = the pre-activation of act 2).  image: a block image the caller holds
+    (`linear_x6r`).  count: the CALLS key of a block-image launch.  Allocates and reshapes nothing."""
+    if want_word and cfg == 2:
+        raise ValueError("vit_linear_x6r_fwd cfg 2 cannot publish its output's |max| (include/vit_ops.h)")
+    wp = image if image is not None else _linear_image(weight, cfg != 0, transposed)
+    if operand_word is not None:
+        _announce(operand_word)
+    word = _output_amax_word(a2.device) if want_word else None
+    b, r, p = bias.data_ptr() if bias is not None else None, residual.data_ptr() if residual is not None else None, pre.data_ptr() if pre is not None else None
+    if cfg:
+        if count is not None:
+            CALLS[count] = CALLS.get(count, 0) + 1
+        rc = load().vit_linear_x6r_fwd(a2.data_ptr(), wp.data_ptr(), b, r, out.data_ptr(), p, M, N, K, act, cfg, _stream(a2.device))
+    else:
+        rc = load().vit_linear_x6_fwd(a2.data_ptr(), wp.data_ptr(), b, r, out.data_ptr(), p, M, N, K, act, _stream(a2.device))
+    if rc:
+        _check(rc, ("vit_linear_x6r_fwd" if cfg else "vit_linear_x6_fwd") + what)
+    return word
 
 
 class _FusedLinear(torch.autograd.Function):
@@ -1539,48 +1578,33 @@ class _FusedLinear(torch.autograd.Function):
         b = bias.contiguous().float() if bias is not None else None
         x6 = _x6()
         w = weight.contiguous().float()
-        args = (b.data_ptr() if b is not None else None, res2.data_ptr() if res2 is not None else None, out.data_ptr(),
-                pre.data_ptr() if pre is not None else None, M, N, K, int(act), _stream(x.device))
-        ring = _ring_cfg(M, N, K) if x6 else 0
         ctx.ax = None
-        f16 = x6 and _f16()
-        # f16x3: |max| of the input (shared with the weight-gradient launch).  An fc2 takes the word its fc1's epilogue filled (GeluLink.ax)
-        # instead of a pass over the (M, 4 C) hidden activation; an fc1 asks its own epilogue for that word
-        publish = f16 and link is not None and need_pre and ring in (0, 1, 3, 5)
-        # amax_out: the consumer of this layer's output wants its |max| (the attention kernels in f16x3: q, k, v scales) -- the epilogue publishes it
-        out_word = None
         ctx.amax_dx = bool(amax_dx)
-
-        def operands():
-            nonlocal out_word
-            if not f16:
-                return
-            ctx.ax = link_in.ax if (link_in is not None and link_in.ax is not None) else _amax_of(x2)
-            _announce(ctx.ax)
-            if publish:
-                link.ax = _output_amax_word(x2.device)
-            elif amax_out and PUBLISH_AMAX and ring in (0, 1, 3, 5) and act == 0:
-                out_word = _output_amax_word(x2.device)
-        if (x6 and PAIR_SPLIT and x.requires_grad and N % 16 == 0 and K % 8 == 0
-                and _SPLIT_CACHE.get(_image_key(weight, "block" if ring else "row"), weight) is None):
-            # the forward image is stale (the optimizer stepped): the backward's input-gradient GEMM will need the transposed image of the
-            # same values -- both in one launch, each in the layout its kernel takes (the dX dispatch rule of `backward` below)
-            split_weight_pair(weight, bool(ring), bool(_ring_cfg_dx(M, N, K)))
-        if ring:
-            # LDS-DMA ring kernels (csrc/vit_gemm_x6r.hip), bit-identical to vit_linear_x6_fwd: taken on the shapes where
-            # tools/probes/gemm_lab.py measured them faster (per arithmetic mode: _RING_SHAPES)
-            CALLS["linear_x6r"] += 1
-            wpb = split_weight_block(weight)
-            operands()
-            _check(load().vit_linear_x6r_fwd(x2.data_ptr(), wpb.data_ptr(), *args[:-1], ring, args[-1]), "vit_linear_x6r_fwd")
-        elif x6:
-            wp = split_weight(weight)
-            operands()
-            _check(load().vit_linear_x6_fwd(x2.data_ptr(), wp.data_ptr(), *args), "vit_linear_x6_fwd")
+        if x6:
+            cfg = _linear_cfg(M, N, K)
+            if (PAIR_SPLIT and x.requires_grad and N % 16 == 0 and K % 8 == 0
+                    and _SPLIT_CACHE.get(_image_key(weight, _LINEAR_LAYOUTS[2 * (cfg != 0)]), weight) is None):
+                # the forward image is stale (the optimizer stepped): the backward's input-gradient GEMM will need the transposed image of the
+                # same values -- both in one launch, each in the layout the route of its launch reads
+                split_weight_pair(weight, cfg != 0, _linear_cfg(M, N, K, dx=True) != 0)
+            # f16x3: |max| of the input (shared with the weight-gradient launch).  An fc2 takes the word its fc1's epilogue filled (GeluLink.ax)
+            # instead of a pass over the (M, 4 C) hidden activation; an fc1 asks its own epilogue for that word (to_link).
+            # amax_out: the consumer of this layer's output wants its |max| (the attention kernels in f16x3: q, k, v scales) -- the epilogue publishes it
+            to_link = to_publish = False
+            if _f16():
+                ctx.ax = link_in.ax if (link_in is not None and link_in.ax is not None) else _amax_of(x2)
+                to_link = link is not None and need_pre
+                to_publish = not to_link and amax_out and PUBLISH_AMAX and act == 0
+            word = _launch_linear(x2, weight, out, M, N, K, cfg, bias=b, residual=res2, pre=pre, act=int(act), operand_word=ctx.ax,
+                                  want_word=to_link or to_publish)
+            if to_link:
+                link.ax = word
+            elif to_publish:
+                _publish(out, word)
         else:
-            _check(load().vit_linear_fwd(x2.data_ptr(), w.data_ptr(), *args), "vit_linear_fwd")
-        if out_word is not None:
-            _publish(out, out_word)
+            _check(load().vit_linear_fwd(x2.data_ptr(), w.data_ptr(), b.data_ptr() if b is not None else None,
+                                         res2.data_ptr() if res2 is not None else None, out.data_ptr(), pre.data_ptr() if pre is not None else None,
+                                         M, N, K, int(act), _stream(x.device)), "vit_linear_fwd")
         ctx.save_for_backward(x2, w, pre)
         # GeluLink: `link` (this layer applies the GELU) publishes its pre-activation; `link_in` (this layer consumes that GELU's
         # output) lets the backward run GELU' inside its input-gradient GEMM -- see GeluLink
@@ -1619,47 +1643,27 @@ class _FusedLinear(torch.autograd.Function):
                 ag = _amax_of(t)
             return ag
 
-        dx_word = None
-
-        def publish_dx(lk, ring):
-            nonlocal dx_word
-            # (fc2, GELU' in the epilogue: the stored values ARE fc1's dY)
-            if f16 and lk is not None and gelu_pre is not None and ring in (0, 1, 3, 5):
-                lk.adx = _output_amax_word(g.device)
-            elif f16 and ctx.amax_dx and PUBLISH_AMAX and gelu_pre is None and ring in (0, 1, 3, 5):
-                # (proj: its input gradient is the attention backward's dO, whose f16x3 scale comes from this word)
-                dx_word = _output_amax_word(g.device)
         dx = None
         if need_x:
             N, K = w.shape
             if ctx.weight_ref is not None and N % 16 == 0:
                 g2c = g2.contiguous().float()
-                dx = torch.empty((g2c.shape[0], K), dtype=torch.float32, device=g.device)
+                M = g2c.shape[0]
+                dx = torch.empty((M, K), dtype=torch.float32, device=g.device)
                 lk = ctx.link_in
-                gelu_pre = lk.pre if (lk is not None and lk.pre is not None and tuple(lk.pre.shape) == (g2c.shape[0], K)) else None
-                ring = _ring_cfg_dx(g2c.shape[0], N, K) if ctx.mode == LINEAR_MODE else 0
-                if ring:
-                    CALLS["linear_x6r"] += 1
-                    wpb = split_weight_block(ctx.weight_ref, True)
-                    if f16:
-                        _announce(amax_g(g2c))
-                    publish_dx(lk, ring)
-                    _check(load().vit_linear_x6r_fwd(g2c.data_ptr(), wpb.data_ptr(), None,
-                                                     gelu_pre.data_ptr() if gelu_pre is not None else None, dx.data_ptr(), None,
-                                                     g2c.shape[0], K, N, 2 if gelu_pre is not None else 0, ring, _stream(g.device)), "vit_linear_x6r_fwd (dX)")
-                else:
-                    wpt = split_weight(ctx.weight_ref, True)
-                    if f16:
-                        _announce(amax_g(g2c))
-                    publish_dx(lk, 0)
-                    _check(load().vit_linear_x6_fwd(g2c.data_ptr(), wpt.data_ptr(), None,
-                                                    gelu_pre.data_ptr() if gelu_pre is not None else None,
-                                                    dx.data_ptr(), None, g2c.shape[0], K, N, 2 if gelu_pre is not None else 0, _stream(g.device)),
-                           "vit_linear_x6_fwd (dX)")
+                gelu_pre = lk.pre if (lk is not None and lk.pre is not None and tuple(lk.pre.shape) == (M, K)) else None
+                # f16x3, the |max| of what the epilogue stores: behind a GELU those values ARE fc1's dY (GeluLink.adx); amax_dx: proj's input
+                # gradient is the attention backward's dO, whose scale comes from the published word
+                want = f16 and (gelu_pre is not None or (ctx.amax_dx and PUBLISH_AMAX))
+                word = _launch_linear(g2c, ctx.weight_ref, dx, M, K, N, _linear_cfg(M, N, K, dx=True, mode=ctx.mode), transposed=True,
+                                      residual=gelu_pre, act=2 if gelu_pre is not None else 0, operand_word=amax_g(g2c) if f16 else None,
+                                      want_word=want, what=" (dX)")
                 if gelu_pre is not None:
                     lk.fused = True
-                if dx_word is not None:
-                    _publish(dx, dx_word)
+                    if want:
+                        lk.adx = word
+                elif want:
+                    _publish(dx, word)
                 dx = dx.reshape(shp)
             else:
                 dx = (g2 @ w).reshape(shp)
@@ -1706,7 +1710,7 @@ class _FusedLinear(torch.autograd.Function):
 
 
 SMALL_M_ROWS = int(os.environ.get("VIT_SMALL_M_ROWS", "1024"))      # launches of up to this many rows take csrc/vit_gemm_sm.hip; 0 = the kernel is off at every M (A/B switch)
-NARROW_N = int(os.environ.get("VIT_NARROW_N", "768"))               # ... and launches of ANY row count whose output is at most this wide (0 = off): see _ring_cfg
+NARROW_N = int(os.environ.get("VIT_NARROW_N", "768"))               # ... and launches of ANY row count whose output is at most this wide (0 = off): see _linear_cfg
 _SMALL_M_SET: dict = {}                                              # host thread -> the max_rows this thread last told the library
 
 
@@ -1766,24 +1770,13 @@ def fused_linear(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, resid
             res2 = residual.reshape(-1, N)
             if not res2.is_contiguous() or res2.dtype != torch.float32:
                 res2 = res2.contiguous().float()
-        small = small_m_kernel(M, N, K)
-        wp = split_weight_block(weight) if small else split_weight(weight)
-        ow = None
-        if _f16():
-            _announce(_amax_of(x2))
-            # the small-M kernel (csrc/vit_gemm_sm.hip) runs the whole epilogue in one launch, GELU included: every output gets its |max| word
-            # for free (the next Linear / the attention finds it published); the 128-row kernel publishes un-activated outputs on request
-            if PUBLISH_AMAX and ((amax_out and not gelu) or small):
-                ow = _output_amax_word(x2.device)
-        if small:
-            CALLS["linear_sm"] = CALLS.get("linear_sm", 0) + 1
-            _check(load().vit_linear_x6r_fwd(x2.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                             res2.data_ptr() if res2 is not None else None, out.data_ptr(), None, M, N, K,
-                                             1 if gelu else 0, 5, _stream(x.device)), "vit_linear_x6r_fwd (small M)")
-        else:
-            _check(load().vit_linear_x6_fwd(x2.data_ptr(), wp.data_ptr(), bias.data_ptr() if bias is not None else None,
-                                            res2.data_ptr() if res2 is not None else None, out.data_ptr(), None, M, N, K,
-                                            1 if gelu else 0, _stream(x.device)), "vit_linear_x6_fwd")
+        cfg = _linear_cfg(M, N, K, serving=True)
+        # f16x3: the small-M kernel (csrc/vit_gemm_sm.hip) runs the whole epilogue in one launch, GELU included: every output gets its |max| word
+        # for free (the next Linear / the attention finds it published); the 128-row kernel publishes un-activated outputs on request
+        f16 = _f16()
+        ow = _launch_linear(x2, weight, out, M, N, K, cfg, bias=bias, residual=res2, act=1 if gelu else 0, operand_word=_amax_of(x2) if f16 else None,
+                            want_word=f16 and PUBLISH_AMAX and ((amax_out and not gelu) or cfg != 0), count="linear_sm",
+                            what=" (small M)" if cfg else "")
         if ow is not None:
             _publish(out, ow)
         return out.reshape(*shp[:-1], N)

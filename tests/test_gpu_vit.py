@@ -625,7 +625,7 @@ def test_layernorm_kernels_match_fp64_with_and_without_skip(shape, bias):
 def test_no_grad_fast_paths_equal_the_autograd_paths(monkeypatch):
     """serving: under no_grad fused_linear and LayerNorm skip the autograd node and go straight to the kernels; with the same kernel behind
     both paths (round 6: at up to 1 024 rows the no-grad Linear takes csrc/vit_gemm_sm.hip, the autograd path keeps the 128-row kernel --
-    vit_ops._ring_cfg) the results are the same bits as the autograd path's forward; with the small-M kernel they agree to fp32 round-off"""
+    vit_ops._linear_cfg) the results are the same bits as the autograd path's forward; with the small-M kernel they agree to fp32 round-off"""
     from styl3r_amd import vit_ops
     from styl3r_amd.vit_ops import LayerNorm, fused_linear
     torch.manual_seed(11)

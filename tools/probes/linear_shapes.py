@@ -26,12 +26,13 @@ batch = dict(context=dict(image=torch.rand(b, v_ctx, 3, H, H, device=dev, genera
                          intrinsics=ex(sc.intrinsics, -1, -1, -1), near=ex(sc.near, -1), far=ex(sc.far, -1)))
 step(batch)
 seen = collections.Counter()
-orig = vit_ops._ring_cfg
-def spy(M, N, K):
-    r = orig(M, N, K)
-    seen[(M, N, K, r)] += 1
+orig = vit_ops._linear_cfg
+def spy(M, N, K, **kw):
+    r = orig(M, N, K, **kw)
+    if not kw:                       # (a dX route asks again with N and K exchanged: that inner call is the one counted)
+        seen[(M, N, K, r)] += 1
     return r
-vit_ops._ring_cfg = spy
+vit_ops._linear_cfg = spy
 step(batch); torch.cuda.synchronize()
 tot = sum(2.0 * M * N * K * c for (M, N, K, r), c in seen.items())
 print(f"| M | N | K | ring cfg | launches | GFLOP each | share of the Linear fwd+dX FLOPs |\n|---|---|---|---|---|---|---|")

@@ -36,7 +36,7 @@ for name, (N, K) in {"enc_qkv": (3072, 1024), "enc_fc1": (4096, 1024), "enc_fc2"
     us = timeit(wgrad)
     print(json.dumps({"lib": tag, "kernel": "wgrad", "shape": name, "us": round(us, 1), "TF3": round(3 * 2 * M * N * K / us / 1e6, 1)}), flush=True)
     wt = torch.nn.Parameter(w); xr = x.clone().requires_grad_(True)
-    ring = vit_ops._ring_cfg(M, N, K)
+    ring = vit_ops._linear_cfg(M, N, K)
     us = timeit(lambda: vit_ops._FusedLinear.apply(xr, wt, None, None, 0))
     print(json.dumps({"lib": tag, "kernel": f"linear_fwd(ring cfg {ring})", "shape": name, "us": round(us, 1), "TF3": round(3 * 2 * M * N * K / us / 1e6, 1)}), flush=True)
     with torch.no_grad():
