@@ -383,6 +383,26 @@ int vit_lpips_bwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, const
 int vit_maxpool2x2_fwd(const float *in, float *out, int64_t planes, int H, int W, void *stream);
 int vit_maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, void *stream);
 
+/*
+ * The AdaAttN loss (loss_adaattn.py; csrc/vit_adaattn.hip has the design).  vit_adaattn_stats, forward only: q_hat (Bq, D, Nq) and
+ * k_hat (Bs, D, M) instance-normalised, s (Bs, C, M), all fp32 and contiguous; image b attends to style row style_index[b] (the views of a
+ * scene share one style: keys and values are stored once per style).  With A = softmax_m(q_hat^T k_hat), unscaled,
+ *     mean (Bq, C, Nq) = A s,     std (Bq, C, Nq) = sqrt(relu(A s^2 - mean^2)).
+ * Online softmax on the exact-f32 MFMA; the attention matrix never reaches global memory; every output element is written once (no
+ * zero-fill, no atomics, bit-identical run to run); Nq, M >= 1 arbitrary.  style_index: HOST array (Bq), checked before the launch;
+ * style_index_dev: the same values on the device.  VIT_EINVAL before any launch for a null pointer, D % 64, C % 64, D > 448, C > 256
+ * (VGG layers 4 - 5 stay on the framework expression), M or Nq < 1, Bq > 65535 or an index outside [0, Bs).
+ * vit_adaattn_l1: p, c, mean, std (B, C, N) -> cs = instance_norm(c) std + mean (per (image, channel), biased variance, eps 1e-5),
+ *     *loss = sum |p - cs| / numel,   grad = sign(p - cs) / numel  (sign(0) = 0),   cs (or NULL) = cs itself.
+ * Two launches: the pass (one workgroup per (image, channel), float64 partials into scratch, vit_adaattn_l1_scratch_bytes, 8-byte
+ * aligned) and a one-workgroup fold in index order.  No atomics.
+ */
+int vit_adaattn_stats(const float *q_hat, const float *k_hat, const float *s, const int32_t *style_index, const int32_t *style_index_dev,
+                      int Bq, int Bs, int D, int C, int Nq, int M, float *mean, float *std, void *stream);
+size_t vit_adaattn_l1_scratch_bytes(int B, int C);
+int vit_adaattn_l1(const float *p, const float *c, const float *mean, const float *std, int B, int C, int N, void *scratch, float *loss,
+                   float *grad, float *cs, void *stream);
+
 const char *vit_version(void);
 const char *vit_last_error(void);
 

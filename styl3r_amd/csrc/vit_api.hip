@@ -66,6 +66,11 @@ int lpips_fwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, float *di
 int lpips_bwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, const float *g, const float *stats, hipStream_t stream);
 int maxpool2x2_fwd(const float *in, float *out, int64_t planes, int H, int W, hipStream_t stream);
 int maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, hipStream_t stream);
+int adaattn_stats(const float *q, const float *k, const float *s, const int32_t *index_host, const int32_t *index_dev, int Bq, int Bs, int D,
+                  int C, int Nq, int M, float *mean, float *std, hipStream_t stream);
+size_t adaattn_l1_scratch_bytes(int B, int C);
+int adaattn_l1(const float *p, const float *c, const float *mean, const float *std, int B, int C, int N, void *scratch, float *loss, float *grad,
+               float *cs, hipStream_t stream);
 int linear_sm_set(int max_rows, int tm, int nw);
 int linear_sm_ok(int M, int N, int K);
 int linear_sm_grouped(const float *const *x, const void *const *wpb, const float *const *bias, const float *const *residual, float *const *out,
@@ -313,6 +318,20 @@ VIT_EXPORT int vit_maxpool2x2_fwd(const float *in, float *out, int64_t planes, i
 VIT_EXPORT int vit_maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, void *stream)
 {
     return vit::maxpool2x2_bwd(in, dout, din, planes, H, W, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT int vit_adaattn_stats(const float *q_hat, const float *k_hat, const float *s, const int32_t *style_index, const int32_t *style_index_dev,
+                                 int Bq, int Bs, int D, int C, int Nq, int M, float *mean, float *std, void *stream)
+{
+    return vit::adaattn_stats(q_hat, k_hat, s, style_index, style_index_dev, Bq, Bs, D, C, Nq, M, mean, std, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT size_t vit_adaattn_l1_scratch_bytes(int B, int C) { return vit::adaattn_l1_scratch_bytes(B, C); }
+
+VIT_EXPORT int vit_adaattn_l1(const float *p, const float *c, const float *mean, const float *std, int B, int C, int N, void *scratch, float *loss,
+                              float *grad, float *cs, void *stream)
+{
+    return vit::adaattn_l1(p, c, mean, std, B, C, N, scratch, loss, grad, cs, static_cast<hipStream_t>(stream));
 }
 
 VIT_EXPORT const char *vit_version(void) { return "vit-hip gfx950 0.1.0"; }

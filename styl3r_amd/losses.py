@@ -5,6 +5,7 @@ Mirrors
   * `LossStyle`      src/loss/loss_style.py:25-79   (VGG19 relu1_1 / 2_1 / 3_1 / 4_1 mean-std style + content)
   * `IdentityLoss`   src/loss/loss_identity.py:13-52
   * `VGGEncoder`, `calc_mean_std`   src/test/vgg_model.py:19-28,79-98
+  * `LossAdaAttN`, `NormalizedVGG`  src/loss/loss_adaattn.py:61-191, src/model/encoder/stylizer/stylizer.py:23-73, stylizer/vgg.py:5-92
 torchvision is not installed and the ImageNet VGG19 weights cannot be downloaded: `VGGEncoder` rebuilds the
 `vgg19().features[:21]` stack with torchvision's parameter names (`N.weight`, N in 0,2,5,7,10,12,14,16,19), so
 `load_vgg19_features(state_dict)` accepts the stock `vgg19-dcbb9e9d.pth` when it is available; until then the
@@ -658,14 +659,309 @@ class Regr3D(nn.Module):
         return regr3d_expression(gt_pts1, gt_pts2, pr_pts1, pr_pts2, conf1, conf2, self.norm_mode, self.gt_scale, dist_clip, disable_view1)
 
 
+# ---------------------------------------------------------------------------
+# AdaAttN loss (src/loss/loss_adaattn.py:61-191, AdaAttN of src/model/encoder/stylizer/stylizer.py:23-73, NormalizedVGG of
+# stylizer/vgg.py:5-92): L1 between the prediction's VGG features and the target's features re-styled by attention-weighted style
+# statistics, plus lam x the MSE of spatial feature statistics against the style's.  The stylised target depends on the target and the
+# style only: it is computed without a graph, on the kernels of csrc/vit_adaattn.hip for device tensors.
+# ---------------------------------------------------------------------------
+CALLS.update({"adaattn_hip_stats": 0, "adaattn_expr_stats": 0, "adaattn_hip_l1": 0})
+ADAATTN_MAX_D, ADAATTN_MAX_C = 448, 256        # what vit_adaattn_stats takes (VGG layers 1 - 3); beyond it: the expression
+# make_vgg() as (kind, c_in, c_out): every 3 x 3 convolution is [ReflectionPad2d(1), Conv2d, ReLU] (three Sequential indices), the 1 x 1
+# input convolution and the pools take one index each; "end": a slice ends after the ReLU of conv{k}_1
+_NVGG_OPS = (("c1", 3, 3), ("c3", 3, 64), "end", ("c3", 64, 64), "pool", ("c3", 64, 128), "end", ("c3", 128, 128), "pool", ("c3", 128, 256), "end",
+             ("c3", 256, 256), ("c3", 256, 256), ("c3", 256, 256), "pool", ("c3", 256, 512), "end",
+             ("c3", 512, 512), ("c3", 512, 512), ("c3", 512, 512), "pool", ("c3", 512, 512), "end")
+_NVGG_SLICE_ENDS = (4, 11, 18, 31, 44)
+
+
+class NormalizedVGG(nn.Module):
+    """relu1_1 .. relu{depth}_1 of the "normalised" VGG19 (a 1 x 1 input convolution, reflection padding in front of every 3 x 3 convolution,
+    max-pooling) on images in [0, 1] without ImageNet normalisation.  Parameter names are the reference's: `slice{k}.{N}.weight / .bias`, N the
+    index in its nn.Sequential.  Frozen.  Only the slices up to `depth` exist and run (the reference always runs all five and so refuses
+    images under 32 pixels a side).  On the GPU the eligible convolutions run on Conv2dX6: a reflect-padded 3 x 3 convolution is the
+    zero-padded convolution of the reflect-padded input with one border pixel cropped."""
+
+    def __init__(self, depth: int = 5):
+        super().__init__()
+        assert 1 <= depth <= 5, depth
+        self.depth = depth
+        self.all_keys = []                                                   # the bare Sequential's keys of all five slices, in order
+        idx, k, block = 0, 1, nn.Sequential()
+        for op in _NVGG_OPS:
+            if op == "end":
+                if k <= depth:
+                    setattr(self, f"slice{k}", block)
+                k, block = k + 1, nn.Sequential()
+            elif op == "pool":
+                idx += 1
+            else:
+                kind, ci, co = op
+                idx += kind == "c3"                                          # its ReflectionPad2d
+                if k <= depth:
+                    block.add_module(str(idx), nn.Conv2d(ci, co, 1) if kind == "c1" else Conv2dX6(ci, co, 3, padding=1))
+                self.all_keys += [f"{idx}.weight", f"{idx}.bias"]
+                idx += 1 if kind == "c1" else 2                              # the convolution (and its ReLU)
+        assert idx == _NVGG_SLICE_ENDS[-1]
+        self.requires_grad_(False)
+
+    def load_normalised_vgg(self, state_dict: dict):
+        """`vgg_normalised.pth`: the state dict of the bare nn.Sequential (`0.weight`, `2.weight`, `5.weight`, ...).  Strict: its keys must be
+        exactly the 17 convolutions' weights and biases; those of slices beyond `depth` are checked by name and not kept."""
+        _same_keys(set(state_dict), set(self.all_keys), "vgg_normalised")
+        sd = {}
+        for key, val in state_dict.items():
+            k = 1 + sum(int(key.split(".")[0]) >= e for e in _NVGG_SLICE_ENDS)
+            if k <= self.depth:
+                sd[f"slice{k}.{key}"] = val
+        return self.load_state_dict(sd, strict=True)
+
+    @staticmethod
+    def _conv3_relu(m, x: Tensor) -> Tensor:
+        xp = F.pad(x, (1, 1, 1, 1), mode="reflect")
+        # not in "bf16x3": its products leave out the 2^-16-level terms, and the unscaled AdaAttN logits (sums of hundreds of feature products in
+        # front of an exp) need features of fp32 quality; that mode keeps the library's fp32 convolution here
+        if vit_ops.LINEAR_MODE != "bf16x3" and m._x6_ok(xp):
+            return torch.relu(m(xp)[..., 1:-1, 1:-1])
+        return torch.relu(F.conv2d(xp, m.weight, m.bias))
+
+    def forward(self, x: Tensor) -> list:
+        feats = []
+        for k in range(1, self.depth + 1):
+            convs = list(getattr(self, f"slice{k}"))
+            for m in convs[:-1]:                                             # slice 1: the 1 x 1 input map; later slices: conv{k-1}_2 ..
+                x = m(x) if k == 1 else self._conv3_relu(m, x)
+            if k > 1:
+                x = vit_ops.maxpool2x2(x)
+            x = self._conv3_relu(convs[-1], x)
+            feats.append(x)
+        return feats
+
+
+def _adaattn_qk(feats: list, upto: int) -> list:
+    """the cumulative query / key stacks of VGGContentLoss: q_0 = f_0, q_i = cat(bilinear(q_{i-1} -> size of f_i), f_i) -- relu1_1 is
+    resampled once per level, not once by the total factor"""
+    q, out = feats[0], [feats[0]]
+    for f in feats[1:upto]:
+        q = torch.cat([F.interpolate(q, size=f.shape[-2:], mode="bilinear", align_corners=False), f], 1)
+        out.append(q)
+    return out
+
+
+def adaattn_stats_expression(q_hat: Tensor, k_hat: Tensor, s: Tensor, style_index: Tensor | None = None):
+    """AdaAttN.forward's statistics as plain torch ops: q_hat (Bq, D, Nq), k_hat (Bs, D, M), s (Bs, C, M) -> mean, std (Bq, C, Nq)"""
+    if style_index is not None:
+        k_hat, s = k_hat[style_index.to(k_hat.device, torch.long)], s[style_index.to(s.device, torch.long)]
+    attn = F.softmax(torch.bmm(q_hat.transpose(2, 1), k_hat), -1)
+    st = s.transpose(2, 1)
+    mean = torch.bmm(attn, st)
+    var = F.relu(torch.bmm(attn, st ** 2) - mean ** 2)
+    return mean.transpose(2, 1), torch.sqrt(var).transpose(2, 1)
+
+
+_ADAATTN_INDEX: dict = {}      # (index values, device) -> (host int32 tensor, device int32 tensor)
+
+
+def _adaattn_index(style_index, bq: int, bs: int, dev):
+    if style_index is None:
+        vals = tuple(range(bq))
+    else:
+        vals = tuple(int(i) for i in style_index.detach().cpu().reshape(-1).tolist())      # (a device index is read back: pass a CPU tensor)
+    key = (vals, str(dev))
+    if key not in _ADAATTN_INDEX:
+        if len(_ADAATTN_INDEX) > 64:
+            _ADAATTN_INDEX.clear()
+        host = torch.tensor(vals, dtype=torch.int32)
+        _ADAATTN_INDEX[key] = (host, host.to(dev))
+    return _ADAATTN_INDEX[key]
+
+
+def adaattn_stats(q_hat: Tensor, k_hat: Tensor, s: Tensor, style_index: Tensor | None = None):
+    """(mean, std), each (Bq, C, Nq): the attention-weighted mean and standard deviation of the style features s (Bs, C, M) under
+    softmax_m(q_hat^T k_hat) (unscaled), q_hat (Bq, D, Nq) and k_hat (Bs, D, M) instance-normalised; image b uses style row style_index[b]
+    (None: Bq == Bs, row b).  Forward only.  fp32 device tensors with D % 64 == 0, D <= 448, C % 64 == 0, C <= 256 run on vit_adaattn_stats
+    (and raise if libvit_hip.so is missing); anything else is `adaattn_stats_expression`.  CALLS counts the route."""
+    if q_hat.dim() != 3 or k_hat.dim() != 3 or s.dim() != 3 or q_hat.shape[1] != k_hat.shape[1] or k_hat.shape[0] != s.shape[0] \
+            or k_hat.shape[2] != s.shape[2] or q_hat.shape[2] < 1 or s.shape[2] < 1:
+        raise ValueError(f"adaattn_stats: q_hat (Bq, D, Nq), k_hat (Bs, D, M), s (Bs, C, M), got {tuple(q_hat.shape)}, {tuple(k_hat.shape)}, {tuple(s.shape)}")
+    (bq, d, nq), (bs, c, m) = q_hat.shape, s.shape
+    if (style_index is None and bq != bs) or (style_index is not None and style_index.numel() != bq):
+        raise ValueError(f"adaattn_stats: {bq} images and {bs} styles need a style_index of {bq} entries")
+    if all(t.is_cuda and t.dtype == torch.float32 for t in (q_hat, k_hat, s)) and d % 64 == 0 and d <= ADAATTN_MAX_D \
+            and c % 64 == 0 and c <= ADAATTN_MAX_C and bq <= 65535:
+        host, devi = _adaattn_index(style_index, bq, bs, q_hat.device)
+        q_hat, k_hat, s = (vit_ops._aligned(t.detach()) for t in (q_hat, k_hat, s))
+        mean, std = torch.empty((bq, c, nq), dtype=torch.float32, device=s.device), torch.empty((bq, c, nq), dtype=torch.float32, device=s.device)
+        CALLS["adaattn_hip_stats"] += 1
+        vit_ops._check(vit_ops.load().vit_adaattn_stats(q_hat.data_ptr(), k_hat.data_ptr(), s.data_ptr(), host.data_ptr(), devi.data_ptr(), bq, bs,
+                                                        d, c, nq, m, mean.data_ptr(), std.data_ptr(), vit_ops._stream(s.device)), "vit_adaattn_stats")
+        return mean, std
+    CALLS["adaattn_expr_stats"] += 1
+    return adaattn_stats_expression(q_hat, k_hat, s, style_index)
+
+
+class _AdaAttnL1Hip(torch.autograd.Function):
+    """mean |p - (instance_norm(c) std + mean)| on vit_adaattn_l1: the pass writes sign(p - cs) / numel beside the loss, the backward is one
+    scale by the upstream gradient.  c, mean and std are ground truth."""
+
+    @staticmethod
+    def forward(ctx, p, c, mean, std, want_cs):
+        lib = vit_ops.load()
+        p, c, mean, std = (vit_ops._aligned(t) for t in (p, c, mean, std))
+        b, ch, n = p.shape
+        dev = p.device
+        scratch = torch.empty(lib.vit_adaattn_l1_scratch_bytes(b, ch) // 8, dtype=torch.float64, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        grad = torch.empty_like(p)
+        cs = torch.empty_like(p) if want_cs else None
+        CALLS["adaattn_hip_l1"] += 1
+        vit_ops._check(lib.vit_adaattn_l1(p.data_ptr(), c.data_ptr(), mean.data_ptr(), std.data_ptr(), b, ch, n, scratch.data_ptr(), loss.data_ptr(),
+                                          grad.data_ptr(), cs.data_ptr() if want_cs else None, vit_ops._stream(dev)), "vit_adaattn_l1")
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(grad)
+        if want_cs:
+            ctx.mark_non_differentiable(cs)
+            return loss, grad, cs
+        return loss, grad, None
+
+    @staticmethod
+    def backward(ctx, g, _g_grad, _g_cs):
+        (grad,) = ctx.saved_tensors
+        return grad * g, None, None, None, None
+
+
+def adaattn_l1(p: Tensor, c: Tensor, mean: Tensor, std: Tensor, details: dict | None = None) -> Tensor:
+    """the content term of one layer: mean |p - cs|, cs = instance_norm(c) * std + mean (per (image, channel) over the positions, biased
+    variance, eps 1e-5), all (B, C, N).  fp32 device tensors with ground-truth c / mean / std go through vit_adaattn_l1; anything else is
+    the plain expression.  `details` receives `cs` and `feature_grad` = sign(p - cs) / numel."""
+    if p.dim() != 3 or not (p.shape == c.shape == mean.shape == std.shape):
+        raise ValueError(f"adaattn_l1: four (B, C, N) tensors of one shape, got {[tuple(t.shape) for t in (p, c, mean, std)]}")
+    if all(t.is_cuda and t.dtype == torch.float32 for t in (p, c, mean, std)) and not (c.requires_grad or mean.requires_grad or std.requires_grad) \
+            and p.numel() > 0:
+        loss, grad, cs = _AdaAttnL1Hip.apply(p, c, mean, std, details is not None)
+        if details is not None:
+            details["cs"], details["feature_grad"] = cs, grad
+        return loss
+    # (one position: the normalised value is 0, as on the kernel; F.instance_norm refuses a single spatial element)
+    cs = (torch.zeros_like(c) if c.shape[-1] == 1 else F.instance_norm(c)) * std + mean
+    if details is not None:
+        details["cs"], details["feature_grad"] = cs.detach(), torch.sign(p.detach() - cs.detach()) / p.numel()
+    return (p - cs).abs().mean()
+
+
+def _gram(x: Tensor) -> Tensor:
+    b, c, h, w = x.shape
+    f = x.reshape(b, c, h * w)
+    return torch.bmm(f, f.transpose(2, 1)) / (c * h * w)
+
+
+def adaattn_style_term(pred_feats: list, style_feats: list, layers, stats, style_index: Tensor | None = None) -> Tensor:
+    """VGGStyleLoss (MSE, mean): spatial mean / unbiased std / Gram matrix of the prediction's features against the style's.  The style's
+    statistics are formed once per style image and repeated per view (identical images have identical statistics)."""
+    rep = (lambda t: t) if style_index is None else (lambda t: t[style_index.to(t.device, torch.long)])
+    loss = 0
+    for l in layers:
+        p, s = pred_feats[l - 1], style_feats[l - 1]
+        if "mean" in stats:
+            loss = loss + F.mse_loss(p.mean((-2, -1)), rep(s.mean((-2, -1))))
+        if "std" in stats:
+            loss = loss + F.mse_loss(p.std((-2, -1)), rep(s.std((-2, -1))))
+        if "gram" in stats:
+            loss = loss + F.mse_loss(_gram(p), rep(_gram(s)))
+    return loss
+
+
+def adaattn_expression(pred_feats: list, content_feats: list, style_feats: list, lam: float = 0.3, content_loss_layers=(3,),
+                       style_loss_layers=(2, 3), style_loss_stats=("mean", "std"), style_index: Tensor | None = None,
+                       details: dict | None = None) -> Tensor:
+    """`LossAdaAttN.forward` after its three VGG passes, as plain torch ops in the inputs' dtype: the CPU path and, in float64, the yardstick
+    of the kernels.  The feature lists hold relu1_1 .. of the prediction (b v images), the target (b v) and the style (one per style image;
+    `style_index` (b v,) maps an image to its style, None: one style per image)."""
+    depth = max(content_loss_layers)
+    with torch.no_grad():
+        qs, ks = _adaattn_qk(content_feats, depth), _adaattn_qk(style_feats, depth)
+    content = 0
+    for l in sorted(content_loss_layers):
+        with torch.no_grad():
+            mean, std = adaattn_stats_expression(F.instance_norm(qs[l - 1].flatten(2)), F.instance_norm(ks[l - 1].flatten(2)),
+                                                 style_feats[l - 1].flatten(2), style_index)
+        cs = (F.instance_norm(content_feats[l - 1].flatten(2)) * std + mean).detach()
+        p = pred_feats[l - 1].flatten(2)
+        content = content + (p - cs).abs().mean()
+        if details is not None:
+            details[f"cs{l}"], details[f"feature_grad{l}"] = cs, torch.sign(p.detach() - cs) / p.numel()
+    style = adaattn_style_term(pred_feats, style_feats, style_loss_layers, style_loss_stats, style_index)
+    if details is not None:
+        details["content"], details["style"] = content.detach(), style.detach()
+    return content + lam * style
+
+
+@dataclass
+class LossAdaAttNCfg:
+    lam: float = 0.3
+    content_loss_layers: tuple = (3,)
+    style_loss_layers: tuple = (2, 3)
+    style_loss_stats: tuple = ("mean", "std")
+
+
+class LossAdaAttN(nn.Module):
+    """content + lam * style of loss_adaattn.py on `prediction.color`, `batch["target"]["image"]` (b, v, 3, H, W) and
+    `batch["style"]["image"]` (b, 3, h, w), all in [0, 1].  The target and the style run through the VGG without a graph and the style once
+    per style image, not per view.  fp32 device tensors: the stylised target's statistics on vit_adaattn_stats (layers 1 - 3; 4 - 5 on the
+    expression), the L1 and its gradient on vit_adaattn_l1; the style term's small statistics stay framework ops (they need autograd).
+    `details` (a dict) receives `content`, `style` and per content layer l `cs{l}` and `feature_grad{l}`."""
+
+    def __init__(self, cfg: LossAdaAttNCfg = LossAdaAttNCfg(), vgg: NormalizedVGG | None = None):
+        super().__init__()
+        self.cfg = cfg
+        layers = [*cfg.content_loss_layers, *cfg.style_loss_layers]
+        if not cfg.content_loss_layers or not all(l in (1, 2, 3, 4, 5) for l in layers):
+            raise ValueError(f"LossAdaAttN: VGG layers are 1 .. 5 and there is at least one content layer, got {cfg}")
+        if not all(s in ("mean", "std", "gram") for s in cfg.style_loss_stats):
+            raise ValueError(f"LossAdaAttN: style statistics are 'mean', 'std', 'gram', got {cfg.style_loss_stats}")
+        self.vgg = (vgg or NormalizedVGG(depth=max(layers))).eval()
+        if self.vgg.depth < max(layers):
+            raise ValueError(f"LossAdaAttN: the VGG ends at relu{self.vgg.depth}_1, the configuration needs relu{max(layers)}_1")
+        for p in self.vgg.parameters():                                     # convert_to_buffer(..., persistent=False)
+            p.requires_grad_(False)
+
+    def forward(self, prediction, batch, gaussians=None, global_step: int = 0, details: dict | None = None) -> Tensor:
+        image, style = batch["target"]["image"], batch["style"]["image"]
+        b, v = image.shape[:2]
+        if style.shape[0] != b:
+            raise ValueError(f"LossAdaAttN: one style image per scene, got {tuple(style.shape)} for {b} scenes")
+        cfg = self.cfg
+        index = torch.arange(b, dtype=torch.int32).repeat_interleave(v)
+        fp = self.vgg(prediction.color.reshape(b * v, *image.shape[2:]))
+        with torch.no_grad():
+            fc, fs = self.vgg(image.reshape(b * v, *image.shape[2:])), self.vgg(style)
+        if not (image.is_cuda and image.dtype == torch.float32 and style.dtype == torch.float32 and prediction.color.dtype == torch.float32):
+            return adaattn_expression(fp, fc, fs, cfg.lam, cfg.content_loss_layers, cfg.style_loss_layers, cfg.style_loss_stats, index, details)
+        depth = max(cfg.content_loss_layers)
+        with torch.no_grad():
+            qs, ks = _adaattn_qk(fc, depth), _adaattn_qk(fs, depth)
+        content = 0
+        for l in sorted(cfg.content_loss_layers):
+            with torch.no_grad():
+                mean, std = adaattn_stats(F.instance_norm(qs[l - 1].flatten(2)), F.instance_norm(ks[l - 1].flatten(2)), fs[l - 1].flatten(2), index)
+            d = {} if details is not None else None
+            content = content + adaattn_l1(fp[l - 1].flatten(2), fc[l - 1].flatten(2), mean, std, d)
+            if details is not None:
+                details[f"cs{l}"], details[f"feature_grad{l}"] = d["cs"], d["feature_grad"]
+        style_term = adaattn_style_term(fp, fs, cfg.style_loss_layers, cfg.style_loss_stats, index)
+        if details is not None:
+            details["content"], details["style"] = content.detach(), style_term.detach()
+        return content + cfg.lam * style_term
+
+
 def get_losses(cfgs) -> list:
-    """the reference's loss registry (src/loss/__init__.py): this module's cfg dataclasses -> their modules, in order.  `adaattn` is the one
-    registered name without a counterpart here."""
-    table = {LossMseCfg: LossMse, LossLpipsCfg: LossLpips, LossStyleCfg: LossStyle, LossDepthCfg: LossDepth}
+    """the reference's loss registry (src/loss/__init__.py): this module's cfg dataclasses -> their modules, in order: mse, lpips, style, depth
+    and adaattn."""
+    table = {LossMseCfg: LossMse, LossLpipsCfg: LossLpips, LossStyleCfg: LossStyle, LossDepthCfg: LossDepth, LossAdaAttNCfg: LossAdaAttN}
     out = []
     for cfg in cfgs:
         if type(cfg) not in table:
-            raise NotImplementedError(f"get_losses: no loss for {cfg!r}; of the reference's registry only `adaattn` is not built (LossAdaAttN is "
-                                      "marked untested there, imports the abandoned stylizer modules and no documented run selects it)")
+            raise NotImplementedError(f"get_losses: no loss for {cfg!r}: an entry is one of this module's cfg dataclasses "
+                                      "(LossMseCfg, LossLpipsCfg, LossStyleCfg, LossDepthCfg, LossAdaAttNCfg; adaattn is LossAdaAttNCfg, not a dict)")
         out.append(table[type(cfg)](cfg))
     return out

@@ -24,10 +24,12 @@ ap.add_argument("--config", choices=["c3", "c4", "c5"], default="c3",
                 help="c3: NVS-pretrain, 2 ctx / 4 tgt views, MSE, everything trains.  c4: style stage, 4 ctx / 6 tgt views, "
                      "VGG style loss + identity pass (two encoder/decoder passes), backbone frozen (random-init VGG: no weights here).  "
                      "c5: stress shapes, 4 ctx views 512x512 -> 1 048 576 Gaussians/scene, sh_degree 4, 4 tgt views 512x512, MSE, all train")
-ap.add_argument("--extra-losses", choices=["lpips", "depth"], default=None,
+ap.add_argument("--extra-losses", choices=["lpips", "depth", "adaattn"], default=None,
                 help="lpips: also time the step with the reference's `/loss: [mse, lpips]` (TrainStep extra_losses=[LossLpips()], LPIPS-VGG on the "
                      "HIP route, random-init weights), in the same process right after the MSE-only step; reported under `with_lpips`.  "
-                     "depth: the same with `/loss: [mse, depth]` (extra_losses=[LossDepth()], config/loss/depth.yaml's values); reported under `with_depth`")
+                     "depth: the same with `/loss: [mse, depth]` (extra_losses=[LossDepth()], config/loss/depth.yaml's values); reported under `with_depth`.  "
+                     "adaattn: the same with `/loss: [mse, adaattn]` (extra_losses=[LossAdaAttN()], config/loss/adaattn.yaml's values, random-init "
+                     "normalised VGG, one random style image per scene); reported under `with_adaattn`")
 args = ap.parse_args()
 assert not (args.extra_losses and args.config == "c4"), "--extra-losses: the c4 step lists its own losses (LossStyle + identity), not the default MSE"
 if args.linear_mode:
@@ -105,6 +107,23 @@ if args.extra_losses == "depth":
                   "value": round(dist_utils.aggregate_throughput(b * v_tgt, args.steps, world, dt_d), 3), "unit": "views/s",
                   "ms_per_step": round(1e3 * dt_d / args.steps, 2), "mse_only_again_ms_per_step": round(1e3 * dt_again / args.steps, 2),
                   "peak_mem_GB": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1)}
+with_adaattn = None
+if args.extra_losses == "adaattn":
+    from styl3r_amd import losses as _losses
+    batch["style"] = dict(image=torch.rand(b, 3, H, H, device=dev, generator=g))      # (a non-stylized encoder ignores it; the loss reads it)
+    step.extra_losses = [_losses.LossAdaAttN().to(dev)]            # same step object: the same encoder, optimizer state and batch
+    torch.cuda.reset_peak_memory_stats(dev)
+    n0 = _losses.CALLS["adaattn_hip_stats"], _losses.CALLS["adaattn_hip_l1"]
+    for _ in range(args.warmup):
+        step(batch)
+    assert _losses.CALLS["adaattn_hip_stats"] > n0[0] and _losses.CALLS["adaattn_hip_l1"] > n0[1], "the AdaAttN loss did not take the HIP route"
+    dt_a = dist_utils.timed_steps(lambda: step(batch), args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)
+    step.extra_losses = []
+    dt_again = dist_utils.timed_steps(lambda: step(batch), args.steps, lambda: torch.cuda.synchronize(dev), dist, dev)      # A / B / A: the spread of the MSE-only step
+    with_adaattn = {"losses": "[mse, adaattn] (mse fused in the composite kernels, LossAdaAttN lam 0.3, content [3], style [2, 3] mean + std)",
+                    "value": round(dist_utils.aggregate_throughput(b * v_tgt, args.steps, world, dt_a), 3), "unit": "views/s",
+                    "ms_per_step": round(1e3 * dt_a / args.steps, 2), "mse_only_again_ms_per_step": round(1e3 * dt_again / args.steps, 2),
+                    "peak_mem_GB": round(torch.cuda.max_memory_allocated(dev) / 2**30, 1)}
 if rank == 0:
     nparam = sum(p.numel() for p in enc.parameters())
     print(json.dumps({"metric": ("512x512" if c5 else "256x256") + " rendered views/sec, full train step (encoder+rasterizer fwd+bwd, AdamW, DP all-reduce)",
@@ -117,6 +136,6 @@ if rank == 0:
                       "buckets": len(step.reducer.buckets), "peak_mem_GB": round(peak_mse / 2**30, 1),
                       "dtype": "f32", "linear_arithmetic": __import__("styl3r_amd.vit_ops", fromlist=["x"]).LINEAR_MODE
 , "data": "synthetic, random-init weights", **({"with_lpips": with_lpips} if with_lpips else {}),
-                      **({"with_depth": with_depth} if with_depth else {})}))
+                      **({"with_depth": with_depth} if with_depth else {}), **({"with_adaattn": with_adaattn} if with_adaattn else {})}))
 if dist is not None:
     dist.barrier(); dist.destroy_process_group()
