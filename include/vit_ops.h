@@ -257,9 +257,21 @@ int vit_linear_x6_wgrad_acc(const float *dy, const float *x, float *dw, float *d
  * `relu_in` is a flag word: bit 0 = ReLU on the input; bit 1 (VIT_CONV_GATE) = `residual` is not added but used as a sign
  * gate, out = residual > 0 ? conv : 0 -- the input gradient of a ReLU-fused convolution with residual := its forward
  * input (bias must be NULL).
+ * Source modes of the 3x3 window (the 2D-AdaIN decoder's ReflectionPad2d(1) and F.interpolate(scale_factor=2) as index maps in the halo
+ * fetch; forward only: no weight gradient and no input gradient exists in these modes):
+ *   bit 2 (VIT_CONV_REFLECT): pixels outside the image are read by reflection without repeating the edge (index -1 -> 1, H -> H - 2, as
+ *     nn.ReflectionPad2d(1)) instead of as zero.  H, W >= 2.
+ *   bit 3 (VIT_CONV_UP2, only together with VIT_CONV_REFLECT): `in` is (B, Ci, H/2, W/2) -- its plane stride is (H/2) (W/2) -- and the window
+ *     reads source pixel (y >> 1, x >> 1) of it after the reflection of (y, x) in the H x W frame: nearest x2 upsampling, then the
+ *     reflection padding.  H and W even; `out` (and `residual`) are (B, Co, H, W).
+ * VIT_EINVAL before anything runs for ksize != 3, VIT_CONV_GATE together with either bit, UP2 without REFLECT, odd H or W with UP2, H < 2
+ * or W < 2.  With a source mode the launch takes the halo kernel at every width.  f16x3: the input's |max| word is the SOURCE tensor's
+ * |max| -- every value the window reads is a value of the source.
  */
 #define VIT_CONV_RELU_IN 1
 #define VIT_CONV_GATE 2
+#define VIT_CONV_REFLECT 4
+#define VIT_CONV_UP2 8
 int vit_conv_x6_fwd(const float *in, const void *w_packed, const float *bias, const float *residual, float *out, int B, int Ci,
                     int Co, int H, int W, int ksize, int relu_in, void *stream);
 
@@ -402,6 +414,27 @@ int vit_adaattn_stats(const float *q_hat, const float *k_hat, const float *s, co
 size_t vit_adaattn_l1_scratch_bytes(int B, int C);
 int vit_adaattn_l1(const float *p, const float *c, const float *mean, const float *std, int B, int C, int N, void *scratch, float *loss,
                    float *grad, float *cs, void *stream);
+
+/*
+ * The 2D-AdaIN baseline (src/test/vgg_model.py AdaIN2D.generate; csrc/vit_adain.hip has the design).
+ * vit_adain_fwd: content (B, C, N), style (Bs, C, M), out (B, C, N), fp32 contiguous; image b uses style row style_index[b] (HOST array,
+ * checked before the launch; style_index_dev: the same values on the device), so the views of a scene share one style whose statistics
+ * are computed once.  Per (image, channel): mean and UNBIASED standard deviation + eps (calc_mean_std), accumulated in float64 in one
+ * fixed order; then, in the reference's operation order,
+ *     t = style_std * (x - c_mean) / c_std + style_mean,    out = alpha * t + (1 - alpha) * x.
+ * Two launches, no atomics, every element written once, bit-identical run to run.  scratch: vit_adain_scratch_bytes(B, Bs, C) bytes,
+ * 4-byte aligned, written before it is read.  VIT_EINVAL before any launch for a null pointer, N < 2 or M < 2 (the unbiased std of one
+ * element is NaN in the reference; the package refuses rather than returns it) or an index outside [0, Bs).
+ * vit_conv3_rgb_fwd: out (B, Co, H, W) = conv3x3(f(in (B, Ci, H, W)), w (Co, Ci, 3, 3) plain fp32) + bias, Ci % 8 == 0, Ci <= 64, Co <= 4:
+ * exact fp32 FMAs on the vector ALU, summed in (ci, ky, kx) order (one chain per eight channels, the chains added in channel order).  flags: VIT_CONV_RELU_IN, VIT_CONV_REFLECT (else zero padding; H, W >= 2
+ * with it); any other bit is VIT_EINVAL.  scale != NULL: out = clamp(y * scale[co] + shift[co], lo, hi) (vgg_denorm in the store);
+ * scale == NULL: y itself.  bias may be NULL.  No atomics, every output written once.
+ */
+size_t vit_adain_scratch_bytes(int B, int Bs, int C);
+int vit_adain_fwd(const float *content, const float *style, const int32_t *style_index, const int32_t *style_index_dev, int B, int Bs, int C,
+                  int64_t N, int64_t M, float alpha, float eps, float *out, void *scratch, void *stream);
+int vit_conv3_rgb_fwd(const float *in, const float *w, const float *bias, const float *scale, const float *shift, float lo, float hi,
+                      float *out, int B, int Ci, int Co, int H, int W, int flags, void *stream);
 
 const char *vit_version(void);
 const char *vit_last_error(void);

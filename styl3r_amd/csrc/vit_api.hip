@@ -71,6 +71,11 @@ int adaattn_stats(const float *q, const float *k, const float *s, const int32_t 
 size_t adaattn_l1_scratch_bytes(int B, int C);
 int adaattn_l1(const float *p, const float *c, const float *mean, const float *std, int B, int C, int N, void *scratch, float *loss, float *grad,
                float *cs, hipStream_t stream);
+size_t adain_scratch_bytes(int B, int Bs, int C);
+int adain_fwd(const float *content, const float *style, const int32_t *index_host, const int32_t *index_dev, int B, int Bs, int C, int64_t N,
+              int64_t M, float alpha, float eps, float *out, void *scratch, hipStream_t stream);
+int conv3_rgb_fwd(const float *in, const float *w, const float *bias, const float *scale, const float *shift, float lo, float hi, float *out,
+                  int B, int Ci, int Co, int H, int W, int flags, hipStream_t stream);
 int linear_sm_set(int max_rows, int tm, int nw);
 int linear_sm_ok(int M, int N, int K);
 int linear_sm_grouped(const float *const *x, const void *const *wpb, const float *const *bias, const float *const *residual, float *const *out,
@@ -332,6 +337,20 @@ VIT_EXPORT int vit_adaattn_l1(const float *p, const float *c, const float *mean,
                               float *grad, float *cs, void *stream)
 {
     return vit::adaattn_l1(p, c, mean, std, B, C, N, scratch, loss, grad, cs, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT size_t vit_adain_scratch_bytes(int B, int Bs, int C) { return vit::adain_scratch_bytes(B, Bs, C); }
+
+VIT_EXPORT int vit_adain_fwd(const float *content, const float *style, const int32_t *style_index, const int32_t *style_index_dev, int B, int Bs,
+                             int C, int64_t N, int64_t M, float alpha, float eps, float *out, void *scratch, void *stream)
+{
+    return vit::adain_fwd(content, style, style_index, style_index_dev, B, Bs, C, N, M, alpha, eps, out, scratch, static_cast<hipStream_t>(stream));
+}
+
+VIT_EXPORT int vit_conv3_rgb_fwd(const float *in, const float *w, const float *bias, const float *scale, const float *shift, float lo, float hi,
+                                 float *out, int B, int Ci, int Co, int H, int W, int flags, void *stream)
+{
+    return vit::conv3_rgb_fwd(in, w, bias, scale, shift, lo, hi, out, B, Ci, Co, H, W, flags, static_cast<hipStream_t>(stream));
 }
 
 VIT_EXPORT const char *vit_version(void) { return "vit-hip gfx950 0.1.0"; }

@@ -592,7 +592,12 @@ __global__ void __launch_bounds__(256, 2) k_conv_x6(const float *__restrict__ in
 // tiles (A: 128 channels x 16 k per tap and slab) stream through two register stages and two LDS images as in k_conv_x6.
 // Per slab and workgroup: 204 halo pixels x 16 channels fetched and split (k_conv_x6: 9 x 128 x 16), 9 x (2 x 2 x NPROD) MFMAs per wave.
 // Epilogue and split-K (gridDim.y) semantics are k_conv_x6's; `amax_out` publishes the |max| of the stored values (unsplit launches).
-template <bool RELU_IN, int NPROD>
+// SRC, the source mode, says where a halo pixel (y, x) of the H x W frame comes from; it enters the up-front h_off / h_m computation and the
+// input's plane stride, nothing else.  0: `in` is H x W, pixels outside the image are zero (padding 1).  1 (VIT_CONV_REFLECT): pixels outside
+// are read by reflection without repeating the edge (-1 -> 1, H -> H - 2: nn.ReflectionPad2d(1)).  2 (REFLECT | UP2): `in` is H/2 x W/2 and
+// the reflected (y, x) reads its pixel (y >> 1, x >> 1) (nearest x2 upsampling, then the reflection padding).  In modes 1 / 2 the only
+// masked halo pixels are those further than one pixel outside the image, which feed nothing but outputs of a ragged tile that are not stored.
+template <bool RELU_IN, int NPROD, int SRC = 0>
 __global__ void __launch_bounds__(256, 2) k_conv3h_x6(const float *__restrict__ in, const uint4 *__restrict__ wp,
                                                       const float *__restrict__ bias, const float *__restrict__ residual,
                                                       float *__restrict__ out, int B, int Ci, int Co, int H, int W, int gate,
@@ -625,7 +630,8 @@ __global__ void __launch_bounds__(256, 2) k_conv3h_x6(const float *__restrict__ 
     const uint4 *wa = wp + ((int64_t)min(co0 + lrow, Co - 1) * KG + kg) * 3;
     // halo loader: 2 k groups x 204 pixels = 408 items of 8 channels; thread -> items tid and tid + 256 (the latter for tid < 152);
     // consecutive lanes = consecutive pixels of a halo row = consecutive addresses of one channel plane
-    const float *inb = in + (int64_t)b_ * Ci * HW;
+    const int IHW = SRC == 2 ? (H >> 1) * (W >> 1) : HW;                         // plane stride of the input
+    const float *inb = in + (int64_t)b_ * Ci * IHW;
     int h_off[2], h_row[2], h_slot[2];
     float h_m[2];
 #pragma unroll
@@ -633,18 +639,26 @@ __global__ void __launch_bounds__(256, 2) k_conv3h_x6(const float *__restrict__ 
         const int item = min(tid + e * 256, 2 * HP - 1);
         const int kq = item / HP, hp = item - kq * HP, hy = hp / HX, hx = hp - hy * HX;
         const int y = ty0 + hy - 1, x = tx0 + hx - 1;
-        h_m[e] = (y >= 0 && y < H && x >= 0 && x < W) ? sb : 0.f;              // border / outside-image pixels contribute zero
-        h_off[e] = (kq * 8) * HW + min(max(y, 0), H - 1) * W + min(max(x, 0), W - 1);
+        if (SRC == 0) {
+            h_m[e] = (y >= 0 && y < H && x >= 0 && x < W) ? sb : 0.f;          // border / outside-image pixels contribute zero
+            h_off[e] = (kq * 8) * HW + min(max(y, 0), H - 1) * W + min(max(x, 0), W - 1);
+        } else {
+            h_m[e] = (y >= -1 && y <= H && x >= -1 && x <= W) ? sb : 0.f;
+            int ry = y < 0 ? -y : y, rx = x < 0 ? -x : x;
+            ry = ry >= H ? 2 * (H - 1) - ry : ry; rx = rx >= W ? 2 * (W - 1) - rx : rx;
+            ry = min(max(ry, 0), H - 1); rx = min(max(rx, 0), W - 1);          // (masked pixels: only the address has to be legal)
+            h_off[e] = SRC == 2 ? (kq * 8) * IHW + (ry >> 1) * (W >> 1) + (rx >> 1) : (kq * 8) * IHW + ry * W + rx;
+        }
         h_row[e] = hp; h_slot[e] = kq * 3;
     }
     const bool second = tid < 2 * HP - 256;
     float hv0[8], hv1[8];
     auto halo_gload = [&](int s) {      // slab s of this split -> registers
-        const float *p0_ = inb + (int64_t)(s_lo + s) * BK * HW;
+        const float *p0_ = inb + (int64_t)(s_lo + s) * BK * IHW;
 #pragma unroll
         for (int c_ = 0; c_ < 8; ++c_) {
-            hv0[c_] = p0_[h_off[0] + c_ * HW];
-            hv1[c_] = p0_[h_off[1] + c_ * HW];                                   // (tid >= 152: a duplicate of the last item, stored to the same place)
+            hv0[c_] = p0_[h_off[0] + c_ * IHW];
+            hv1[c_] = p0_[h_off[1] + c_ * IHW];                                  // (tid >= 152: a duplicate of the last item, stored to the same place)
         }
     };
     auto halo_store = [&](int buf) {
@@ -1257,6 +1271,10 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
                 int H, int W, int ksize, int flags, hipStream_t stream)
 {
     const int relu_in = flags & 1, gate = (flags >> 1) & 1;
+    // source modes of the halo kernel (its template parameter SRC): 0 = zero padding, 1 = REFLECT, 2 = REFLECT | UP2
+    const int src = (flags & VIT_CONV_UP2) ? 2 : ((flags & VIT_CONV_REFLECT) ? 1 : 0);
+    if (src && (ksize != 3 || gate || !(flags & VIT_CONV_REFLECT) || H < 2 || W < 2)) return VIT_EINVAL;
+    if (src == 2 && ((H | W) & 1)) return VIT_EINVAL;
     if (gate && (!residual || bias)) return VIT_EINVAL;
     if (!in || !wp || !out || B <= 0 || Ci <= 0 || Co <= 0 || H <= 0 || W <= 0) return VIT_EINVAL;
     if ((ksize != 1 && ksize != 3) || (Ci % x6::BK) != 0) return VIT_EINVAL;
@@ -1272,20 +1290,26 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
     (void)hipGetLastError();
     // 3x3 layers at least one 32-pixel patch row wide: the halo kernel (one fetch / split per input element instead of nine)
     static const bool taps_only = [] { const char *e = getenv("VIT_CONV3"); return e && e[0] == 't'; }();      // VIT_CONV3=taps: A/B switch
-    if (ksize == 3 && W >= 32 && !taps_only) {
+    // (a source mode takes the halo kernel at EVERY width: its partial-tile masks cope with ragged right and bottom edges down to W = 2)
+    if (ksize == 3 && ((W >= 32 && !taps_only) || src)) {
         const int64_t ht = (int64_t)((Co + x6::BM - 1) / x6::BM) * B * ((W + 31) / 32) * ((H + 3) / 4);
         if (ht > 0x7fffffff) return VIT_EINVAL;
         int S = 1;
         const int nslab = Ci / x6::BK;
-        if (ht < 256) { S = (int)(512 / ht); while (S > 1 && nslab / S < 2) --S; if (S < 1) S = 1; if (S > 8) S = 8; }
+        // (frames narrower than a patch row reach this kernel only through a source mode: there the cap is the tap kernel's 16, so that such a
+        //  launch splits K as finely -- partial sums as short -- as the tap kernel does on the same map materialised)
+        const int s_cap = (src && W < 32) ? 16 : 8;
+        if (ht < 256) { S = (int)(512 / ht); while (S > 1 && nslab / S < 2) --S; if (S < 1) S = 1; if (S > s_cap) S = s_cap; }
         if (S > 1 && !zero_fill(out, (size_t)NP * Co * sizeof(float), stream)) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
-#define VIT_LAUNCH_H6(RL)                                                                                                                                      \
+#define VIT_LAUNCH_H6(RL, SRC)                                                                                                                                 \
     do {                                                                                                                                                        \
-        if (np == 3) hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 3>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out); \
-        else if (np == 2) hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 2>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out); \
-        else hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 6>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out);      \
+        if (np == 3) hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 3, SRC>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out); \
+        else if (np == 2) hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 2, SRC>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out); \
+        else hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 6, SRC>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out);      \
     } while (0)
-        if (relu_in) VIT_LAUNCH_H6(true); else VIT_LAUNCH_H6(false);
+        if (src == 2) { if (relu_in) VIT_LAUNCH_H6(true, 2); else VIT_LAUNCH_H6(false, 2); }
+        else if (src == 1) { if (relu_in) VIT_LAUNCH_H6(true, 1); else VIT_LAUNCH_H6(false, 1); }
+        else { if (relu_in) VIT_LAUNCH_H6(true, 0); else VIT_LAUNCH_H6(false, 0); }
 #undef VIT_LAUNCH_H6
         if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (am_out && S > 1) return amax(out, NP * Co, am_out, stream);      // partial sums: the |max| of the result needs its own pass

@@ -156,14 +156,16 @@ test_step.__test__ = False                       # (not a pytest test function w
 
 
 def validation_step(encoder, decoder, batch: dict, step: int = 0, labeler=None, lpips: Optional[LPIPS] = None, style: Optional[dict] = None,
-                    extra_columns: Sequence = (), resolution: int = 256):
+                    extra_columns: Sequence = (), resolution: int = 256, baseline=None):
     """validation_step (:472-617) for the first scene of `batch` (the reference asserts b == 1): encoder and decoder as `test_step` runs them, the
     three scores as `val/psnr`, `val/ssim`, `val/lpips` (means over the target views) and the three pictures of
     `visualization.validation_images`.  The style is `style` if given, else `batch["style"]` as the reference takes it -- its image rescaled to
     [-1, 1] for an encoder with `stylized` set, and shown unscaled as the Style panel -- else the first context image, without a Style panel
     (the reference needs `batch["style"]`).  Images of the batch are in [0, 1], as everywhere in this package (the reference un-normalises its
     context images here).  The context depth is the dump's depth; more than one value per pixel is averaged (the reference averages exactly
-    three and shows one as it is).  Returns (DecoderOutput, scores, images); logging, the videos and the encoder visualizer stay with the caller."""
+    three and shows one as it is).  `baseline` (a `baseline.AdaIN2D`; None: no such column): "2D Baseline" is the comparison's first column, the
+    target views stylised with the Style panel's image (`batch["style"]`'s, unscaled), else with `style["image"][0]` as given, which must then be
+    in [0, 1].  Returns (DecoderOutput, scores, images); logging, the videos and the encoder visualizer stay with the caller."""
     from .visualization import validation_images
     ctx, tgt = batch["context"], batch["target"]
     _, v, _, h, w = tgt["image"].shape
@@ -187,7 +189,8 @@ def validation_step(encoder, decoder, batch: dict, step: int = 0, labeler=None, 
     context_depth = dump["depth"][0].reshape(ctx["image"].shape[1], *ctx["image"].shape[-2:], -1)
     context_depth = context_depth[..., 0] if context_depth.shape[-1] == 1 else context_depth.mean(dim=-1)
     images = validation_images(ctx["image"][0], context_depth, gt, pred, output.depth[0], gaussians, batch, extra_columns=extra_columns,
-                               style_image=style_panel, labeler=labeler, resolution=resolution)
+                               style_image=style_panel, labeler=labeler, resolution=resolution, baseline=baseline,
+                               baseline_style=None if baseline is None or style_panel is not None else style["image"][0])
     return output, scores, images
 
 

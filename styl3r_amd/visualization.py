@@ -14,7 +14,7 @@ Deviations from the reference:
   * float64 drawing: the reference runs in fp32, where a sub-sample on a primitive's edge can fall on either side (measured: up to 8 pixels
     of a 5-camera 256^2 picture off by 0.25 / 64); `sanitize_*` widen to float64 instead of rounding to fp32;
   * labels come from an injected `labeler(text) -> (3,h,w)` (`pil_labeler` restates annotation.draw_label); `labeler=None` draws none;
-  * the 2D-AdaIN baseline column needs a decoder network the package does not have: callers pass it as an extra column;
+  * the 2D-AdaIN baseline column is drawn when a `baseline.AdaIN2D` is passed (`baseline=`); its style is one row shared by the views;
   * depth panels are coloured through the byte table of `export.pack_frames` (bytes / 255) instead of the fp32 colour map;
   * colours must be finite (a NaN colour never equals itself in the reference's edge rule; it is an argument error here).
 """
@@ -556,13 +556,25 @@ def depth_panels(depth: Tensor) -> Tensor:
     return pack_frames([depth], loop_reverse=False).permute(0, 3, 1, 2).to(torch.float32) / 255
 
 
+def baseline_column(baseline, target_images: Tensor, style_image: Optional[Tensor]) -> tuple:
+    """("2D Baseline", the target views stylised by `baseline`, a `baseline.AdaIN2D`) -- model_wrapper_style.py:536-548: the style image
+    (3,h,w) in [0, 1] is shared by all views (one style row, `style_index` all zero, instead of the reference's row repeated per view)"""
+    if style_image is None:
+        raise ValueError("the 2D baseline stylises the targets with the style image: pass `style_image` (or `baseline_style`)")
+    with torch.no_grad():
+        return "2D Baseline", baseline.stylize(target_images, style_image.to(target_images.device))
+
+
 def comparison_image(context_images: Tensor, context_depth: Tensor, target_images: Tensor, predicted_color: Tensor, predicted_depth: Tensor,
-                     extra_columns: Sequence = (), style_image: Optional[Tensor] = None, labeler: Optional[Labeler] = None) -> Tensor:
+                     extra_columns: Sequence = (), style_image: Optional[Tensor] = None, labeler: Optional[Labeler] = None,
+                     baseline=None, baseline_style: Optional[Tensor] = None) -> Tensor:
     """The `comparison` picture (:528-554) without its border: columns Context (image, depth per view) | Target (Ground Truth) |
-    Target (Prediction) | Depth (Prediction), `extra_columns` = [(label, (n,3,h,w) images)] in front of them (where the reference puts its 2D
-    baseline) and the style image in front of everything.  Images are in [0, 1]."""
+    Target (Prediction) | Depth (Prediction), `extra_columns` = [(label, (n,3,h,w) images)] in front of them and the style image in front of
+    everything.  `baseline` (a `baseline.AdaIN2D`): "2D Baseline" -- the targets stylised with `baseline_style` (default: `style_image`) --
+    is the first column, as in the reference; None: no such column.  Images are in [0, 1]."""
     context = [panel for pair in zip(context_images, depth_panels(context_depth)) for panel in pair]
-    columns = [(label, list(images)) for label, images in extra_columns]
+    columns = [] if baseline is None else [baseline_column(baseline, target_images, style_image if baseline_style is None else baseline_style)]
+    columns = [(label, list(images)) for label, images in (*columns, *extra_columns)]
     columns += [("Context", context), ("Target (Ground Truth)", list(target_images)), ("Target (Prediction)", list(predicted_color)),
                 ("Depth (Prediction)", list(depth_panels(predicted_depth)))]
     comparison = hcat(*[add_label(vcat(*images), label, labeler) for label, images in columns])
@@ -573,13 +585,41 @@ def comparison_image(context_images: Tensor, context_depth: Tensor, target_image
 
 def validation_images(context_images: Tensor, context_depth: Tensor, target_images: Tensor, predicted_color: Tensor, predicted_depth: Tensor,
                       gaussians, batch: dict, extra_columns: Sequence = (), style_image: Optional[Tensor] = None,
-                      labeler: Optional[Labeler] = None, resolution: int = 256) -> dict:
+                      labeler: Optional[Labeler] = None, resolution: int = 256, baseline=None, baseline_style: Optional[Tensor] = None) -> dict:
     """The three pictures validation_step logs for the first scene of `batch`, each fp32 (3,H,W) with `add_border` applied:
-    `comparison` (see `comparison_image`), `projection` = hcat of `render_projections(gaussians)[0]`, `cameras` = hcat of `render_cameras(batch)`.
+    `comparison` (see `comparison_image`; `baseline`, `baseline_style` go to it), `projection` = hcat of `render_projections(gaussians)[0]`,
+    `cameras` = hcat of `render_cameras(batch)`.
     context_images (v,3,h,w) and target_images / predicted_color (t,3,h,w) in [0, 1]; context_depth (v,h,w); predicted_depth (t,h,w)."""
-    comparison = comparison_image(context_images, context_depth, target_images, predicted_color, predicted_depth, extra_columns, style_image, labeler)
+    comparison = comparison_image(context_images, context_depth, target_images, predicted_color, predicted_depth, extra_columns, style_image, labeler,
+                                  baseline=baseline, baseline_style=baseline_style)
     cameras = hcat(*render_cameras(batch, resolution, labeler=labeler))
     images = {"comparison": add_border(comparison), "cameras": add_border(cameras)}
     if gaussians is not None:                                               # (None: no `projection`; it needs the rasterizer and so the GPU)
         images["projection"] = add_border(hcat(*render_projections(gaussians, resolution, labeler=labeler)[0]))
     return images
+
+
+def train_comparison_image(context_images: Tensor, style_images: Tensor, target_images: Tensor, predicted_color: Tensor, predicted_depth: Tensor,
+                           baseline=None, scenes: Optional[Sequence[str]] = None, style_names: Optional[Sequence[str]] = None,
+                           labeler: Optional[Labeler] = None) -> tuple:
+    """The `train/comparison` picture of training_step (:260-308) and its caption, for the FIRST and the LAST sample of the batch, side by
+    side with `add_border` applied: per sample the columns 2D Baseline (the targets stylised by `baseline`, a `baseline.AdaIN2D`; None: no such
+    column) | Context (every context view followed by the style image) | Target (Ground Truth) | Target (Prediction) | Depth (Prediction)
+    under the label "Sample Index: 0" / "Sample Index: -1".  context_images (b,v,3,h,w), style_images (b,3,hs,ws), target_images and
+    predicted_color (b,t,3,h,w) in [0, 1], predicted_depth (b,t,h,w).  Caption: "<scene> | <style name>" of the two samples joined by " | "
+    (the samples' indices where no names are given)."""
+    comparisons, captions = [], []
+    b = target_images.shape[0]
+    for index in (0, -1):
+        style = style_images[index]
+        context = [panel for view in context_images[index] for panel in (view, style)]
+        columns = [] if baseline is None else [baseline_column(baseline, target_images[index], style)]
+        columns = [(label, list(images)) for label, images in columns]
+        columns += [("Context", context), ("Target (Ground Truth)", list(target_images[index])), ("Target (Prediction)", list(predicted_color[index])),
+                    ("Depth (Prediction)", list(depth_panels(predicted_depth[index])))]
+        comparison = hcat(*[add_label(vcat(*images), label, labeler) for label, images in columns])
+        comparisons.append(add_label(comparison, f"Sample Index: {index}", labeler))
+        scene = scenes[index] if scenes is not None else f"sample {index % b}"
+        name = style_names[index] if style_names is not None else f"style {index % b}"
+        captions.append(f"{scene} | {name}")
+    return add_border(hcat(*comparisons)), " | ".join(captions)

@@ -40,12 +40,13 @@ from .weak_cache import WeakTensorCache
 _PKG = Path(__file__).resolve().parent
 _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "lib" / os.environ.get("VIT_LIB_NAME", "libvit_hip.so")     # VIT_LIB_NAME: kernel-experiment builds (tools/ only); the product is libvit_hip.so
-_SOURCES = ["vit_rope.hip", "vit_attention.hip", "vit_attention_tail.hip", "vit_attention_bwd.hip", "vit_gemm.hip", "vit_attention_x6.hip", "vit_attention_bwd_x6.hip", "vit_gemm_x6.hip", "vit_gemm_sm.hip", "vit_gemm_x6r.hip", "vit_resample.hip", "vit_head_tail.hip", "vit_layernorm.hip", "vit_adapter.hip", "vit_optim.hip", "vit_snapshot.hip", "vit_lpips.hip", "vit_adaattn.hip", "vit_api.hip"]
+_SOURCES = ["vit_rope.hip", "vit_attention.hip", "vit_attention_tail.hip", "vit_attention_bwd.hip", "vit_gemm.hip", "vit_attention_x6.hip", "vit_attention_bwd_x6.hip", "vit_gemm_x6.hip", "vit_gemm_sm.hip", "vit_gemm_x6r.hip", "vit_resample.hip", "vit_head_tail.hip", "vit_layernorm.hip", "vit_adapter.hip", "vit_optim.hip", "vit_snapshot.hip", "vit_lpips.hip", "vit_adaattn.hip", "vit_adain.hip", "vit_api.hip"]
 EXPORTS = ("vit_rope2d", "vit_attention_fwd", "vit_attention_set_arith", "vit_attention_arith", "vit_attention_bwd", "vit_linear_fwd", "vit_split_weight_bytes",
            "vit_split_weight", "vit_x6_set_products", "vit_x6_products", "vit_x6_set_operand_amax", "vit_x6_set_output_amax", "vit_amax", "vit_split_weight_block_bytes", "vit_split_weight_block", "vit_split_weight_pair", "vit_split_conv_weight_pair", "vit_split_weights_many", "vit_linear_x6_fwd", "vit_linear_sm_set", "vit_linear_sm_ok", "vit_linear_sm_grouped", "vit_layernorm_fwd_grouped", "vit_linear_x6r_fwd", "vit_linear_x6c_fwd", "vit_linear_x6c_workspace_bytes", "vit_linear_x6c_choose_splits", "vit_linear_x6_wgrad", "vit_linear_x6_wgrad_acc", "vit_conv_x6_fwd", "vit_conv_x6_wgrad", "vit_upsample2x_fwd", "vit_upsample2x_bwd", "vit_relu_dropout_fwd", "vit_relu_dropout_bwd", "vit_layernorm_scratch_bytes", "vit_layernorm_fwd", "vit_layernorm_bwd",
            "vit_adapter_fwd", "vit_adapter_bwd", "vit_head_tail_fwd", "vit_head_tail_bwd", "vit_im2col7", "vit_im2col3_rows", "vit_upsample2x_add_relu_fwd", "vit_adamw_step", "vit_snapshot_chunk_bytes", "vit_snapshot_pack",
            "vit_lpips_scratch_bytes", "vit_lpips_stats_bytes", "vit_lpips_fwd", "vit_lpips_bwd", "vit_maxpool2x2_fwd", "vit_maxpool2x2_bwd",
-           "vit_adaattn_stats", "vit_adaattn_l1_scratch_bytes", "vit_adaattn_l1", "vit_version", "vit_last_error")
+           "vit_adaattn_stats", "vit_adaattn_l1_scratch_bytes", "vit_adaattn_l1",
+           "vit_adain_scratch_bytes", "vit_adain_fwd", "vit_conv3_rgb_fwd", "vit_version", "vit_last_error")
 ERRORS = {-1: "VIT_EINVAL", -3: "VIT_ELAUNCH"}
 _lib = None
 
@@ -248,6 +249,12 @@ def load() -> C.CDLL:
     lib.vit_adaattn_l1_scratch_bytes.restype = C.c_size_t
     lib.vit_adaattn_l1.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.vit_adaattn_l1.restype = C.c_int
+    lib.vit_adain_scratch_bytes.argtypes = [C.c_int, C.c_int, C.c_int]
+    lib.vit_adain_scratch_bytes.restype = C.c_size_t
+    lib.vit_adain_fwd.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, i64, i64, C.c_float, C.c_float, vp, vp, vp]
+    lib.vit_adain_fwd.restype = C.c_int
+    lib.vit_conv3_rgb_fwd.argtypes = [vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    lib.vit_conv3_rgb_fwd.restype = C.c_int
     lib.vit_snapshot_chunk_bytes.argtypes = []
     lib.vit_snapshot_chunk_bytes.restype = C.c_size_t
     lib.vit_snapshot_pack.argtypes = [vp, C.c_int, vp, vp, vp]
