@@ -498,6 +498,38 @@ int gsr_view_overlap(const float *extrinsics, const float *intrinsics, int V, co
                      size_t scratch_bytes, int32_t *counts, void *stream);
 
 /*
+ * Multi-view consistency of rendered colour sets over ONE geometry (csrc/gsr_consistency.hip): view pairs[p][0] (src, i) is warped onto
+ * view pairs[p][1] (dst, j) through dst's depth map and the exact cameras -- a geometric warp, no optical flow -- and compared with dst
+ * where the point is visible in both.
+ *     images (S,V,3,H,W) fp32 planar in [0,1]; depth (V,H,W) fp32, camera-space z in the units of the cameras' translations;
+ *     c2w (V,4,4) and K (V,3,3) FLOAT64 on the device: camera-to-world with an orthonormal rotation (world -> camera is R^T (X - t), no
+ *     inverse is formed) and normalised intrinsics of which only fx, fy, cx, cy are read; pairs (P,2) int32.
+ * Per dst pixel (x, y), in float64 without contraction, in the order of metrics.warp_consistency_expression:
+ *     d = depth[j,y,x] finite and > 0;  u = (x + 0.5) / W, v = (y + 0.5) / H;  Xc = ((u - cx_j) / fx_j * d, (v - cy_j) / fy_j * d, d);
+ *     Xw = R_j Xc + t_j;  Xi = R_i^T (Xw - t_i), z = Xi.z > 0;  px = (fx_i Xi.x / z + cx_i) W - 0.5 in [0, W - 1], py likewise;
+ *     x0 = min(floor(px), W - 2), ax = px - x0 (y likewise): four taps with weights (1-ax)(1-ay), ax(1-ay), (1-ax)ay, ax ay, summed in
+ *     that order;  D = the taps of depth[i], each finite and > 0;  visible: |z - D| <= depth_tol * D.
+ *     Per set s and channel c the taps of images[s,i,c] are summed in float64 and rounded once to fp32: warped[s,p,c,y,x] (0 at invalid
+ *     pixels; warped may be NULL).  The squared difference of that fp32 value and images[s,j,c,y,x], summed over c in float64, goes to
+ *     sse[s,p] (float64 (S,P)); mask[p,y,x] (uint8) is 1 at valid pixels and count[p] (int32) is their number.
+ * A pair that names a view outside [0, V) has no valid pixel (mask 0, count 0, sse 0) and no camera or image is read for it.
+ * Two launches: one lane per dst pixel in tiles of GSR_CONSISTENCY_TILE_W x GSR_CONSISTENCY_TILE_H, one record (count + S float64 sums)
+ * per workgroup, then a one-workgroup fold of the records in a fixed order.  No atomics, bit-identical from run to run; every element
+ * of every output is written on every call.  scratch: the scratch_bytes query's size in device memory, 8-byte aligned, no
+ * initialisation, not shared between concurrent calls (the query answers 0 for dimensions the entry refuses).
+ * GSR_EINVAL before any launch: S < 1 or > GSR_CONSISTENCY_MAX_SETS (callers with more sets call in chunks: the geometry is cheap next
+ * to the colour reads), V < 1, P < 1 or > 2^24, H or W < 2 or > 16384, more than 2^31 - 1 tiles, depth_tol negative or NaN, NULL
+ * images / depth / c2w / K / pairs / mask / count / sse / scratch, scratch not 8-byte aligned.  GSR_ENOSPACE: scratch too small.
+ */
+#define GSR_CONSISTENCY_MAX_SETS 8
+#define GSR_CONSISTENCY_TILE_W 32
+#define GSR_CONSISTENCY_TILE_H 8
+size_t gsr_warp_consistency_scratch_bytes(int64_t P, int S, int H, int W);
+int gsr_warp_consistency(const float *images, const float *depth, const double *c2w, const double *K, const int32_t *pairs, int S, int V,
+                         int64_t P, int H, int W, double depth_tol, float *warped, uint8_t *mask, int32_t *count, double *sse, void *scratch,
+                         size_t scratch_bytes, void *stream);
+
+/*
  * Lens undistortion of 8-bit frames (csrc/gsr_undistort.hip; the reference's COLMAP drivers: initUndistortRectifyMap + remap with
  * INTER_LINEAR and a zero border + the crop to the valid-pixel ROI, per image on the host).  src (N,H,W,3) and dst (N,roi_h,roi_w,3)
  * are interleaved bytes on the device, dst 4-byte aligned.  Frame n belongs to camera frame_cam[n]; frame_cam is an int32 (N) array

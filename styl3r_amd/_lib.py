@@ -18,7 +18,7 @@ _LIBDIR = _PKG / "lib"
 # GSR_LIB_NAME / GSR_HIPCC_EXTRA: kernel-experiment builds (tools/ only); the product is libgsr_hip.so
 LIB_PATH = _LIBDIR / os.environ.get("GSR_LIB_NAME", "libgsr_hip.so")
 
-_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip", "gsr_depth.hip", "gsr_jpeg.hip", "gsr_png.hip", "gsr_jpeg_enc.hip"]
+_SOURCES = ["gsr_forward.hip", "gsr_backward.hip", "gsr_api.hip", "gsr_loss.hip", "gsr_ssim.hip", "gsr_styles.hip", "gsr_pose.hip", "gsr_points.hip", "gsr_outputs.hip", "gsr_inputs.hip", "gsr_views.hip", "gsr_draw.hip", "gsr_undistort.hip", "gsr_depth.hip", "gsr_jpeg.hip", "gsr_png.hip", "gsr_jpeg_enc.hip", "gsr_consistency.hip"]
 _HEADERS = ["gsr_common.h", "gsr_select.h", "gsr_turbo_lut.h", "gsr_jpeg_entropy.h", "../../include/gsr.h"]
 
 HIPCC_FLAGS = [
@@ -142,6 +142,7 @@ GSR_PNG_SRC_U8, GSR_PNG_SRC_F32_PLANAR = 0, 1
 GSR_PNG_ROW_TOO_WIDE = 1                                      # status of gsr_png_chunks / gsr_png_assemble (GSR_OK = 0)
 GSR_JPEG_ENC_SRC_U8, GSR_JPEG_ENC_SRC_F32_PLANAR = 0, 1
 GSR_JPEG_ENC_TOO_LARGE = 1                                    # status of gsr_jpeg_enc_scans (GSR_OK = 0)
+GSR_CONSISTENCY_MAX_SETS, GSR_CONSISTENCY_TILE_W, GSR_CONSISTENCY_TILE_H = 8, 32, 8   # gsr_warp_consistency: sets per call, pixels per workgroup
 GSR_DEPTH_NO_POSITIVE = 1                                     # status[1] of gsr_depth_range
 STAGE_NAMES = ("preprocess", "scan_tiles", "scatter", "tile_sort", "composite_fwd", "composite_bwd", "preprocess_bwd")
 EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_fused", "gsr_backward_fused", "gsr_version", "gsr_profile_create",
@@ -156,7 +157,8 @@ EXPORTS = ("gsr_workspace_layout", "gsr_forward", "gsr_backward", "gsr_forward_f
            "gsr_depth_smooth_scratch_bytes", "gsr_depth_smooth_fwd", "gsr_depth_smooth_bwd",
            "gsr_jpeg_probe", "gsr_jpeg_coef_bytes", "gsr_jpeg_entropy", "gsr_jpeg_scratch_bytes", "gsr_jpeg_pixels",
            "gsr_png_scratch_bytes", "gsr_png_stream_bound", "gsr_png_chunks", "gsr_png_assemble",
-           "gsr_jpeg_enc_scratch_bytes", "gsr_jpeg_enc_stream_bound", "gsr_jpeg_enc_scans")
+           "gsr_jpeg_enc_scratch_bytes", "gsr_jpeg_enc_stream_bound", "gsr_jpeg_enc_scans",
+           "gsr_warp_consistency_scratch_bytes", "gsr_warp_consistency")
 ERRORS = {-1: "GSR_EINVAL (bad dimension / null pointer / unsupported degree)",
           -2: "GSR_ENOSPACE (workspace too small)", -3: "GSR_ELAUNCH (kernel launch failed)"}
 
@@ -289,6 +291,10 @@ def load() -> C.CDLL:
     lib.gsr_jpeg_enc_stream_bound.restype = C.c_size_t
     lib.gsr_jpeg_enc_scans.argtypes = [vp, C.c_int, i64, C.c_int, C.c_int, C.c_int, vp, vp, sz, vp, sz, vp, vp]
     lib.gsr_jpeg_enc_scans.restype = C.c_int
+    lib.gsr_warp_consistency_scratch_bytes.argtypes = [i64, C.c_int, C.c_int, C.c_int]
+    lib.gsr_warp_consistency_scratch_bytes.restype = C.c_size_t
+    lib.gsr_warp_consistency.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, i64, C.c_int, C.c_int, C.c_double, vp, vp, vp, vp, vp, sz, vp]
+    lib.gsr_warp_consistency.restype = C.c_int
     lib.gsr_profile_create.argtypes = [C.c_int]
     lib.gsr_profile_create.restype = C.c_void_p
     lib.gsr_profile_destroy.argtypes = [C.c_void_p]

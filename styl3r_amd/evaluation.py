@@ -258,3 +258,30 @@ def estimate_relative_pose(encoder, decoder, batch: dict, losses: Sequence, cfg:
         e_t, _, e_R = metrics.compute_pose_error(gt, out["pose"].to(gt.device))
         out.update(e_t_ours=e_t, e_R_ours=e_R, e_pose_ours=torch.maximum(e_t, e_R))
     return out
+
+
+# ---- multi-view consistency of a fly-through (metrics.compute_consistency) ------------------------------------------------------------
+def consistency_step(decoder, scene_or_gaussians, context: dict, *, target: Optional[dict] = None, kind: str = "interpolation",
+                     num_frames: int = 60, frames_per_pass: int = 60, gaps=(metrics.SHORT_RANGE_GAP, metrics.LONG_RANGE_GAP),
+                     lpips: Optional[LPIPS] = None, depth_tol: float = 0.05) -> dict:
+    """The score of a stylized scene, which has no ground truth: short- and long-range multi-view consistency of the frames of one
+    fly-through, for the un-stylized render and every style at once (b == 1).
+      scene_or_gaussians  an `inference.StylizedScene`, its list [plain, style 0, ...] of `Gaussians` over one geometry, or one `Gaussians`
+      context / target    as `trajectory.trajectory_cameras` takes them; `kind` and `num_frames` pick the path, WITHOUT the reverse loop of
+                          the videos (a frame pair (t, t + gap) of the way back is a pair of the way out)
+    The float frames come from `inference.render_frames` -- the passes `render_flythrough` runs, `frames_per_pass` cameras each -- then ONE
+    `metrics.compute_consistency` call over all sets: the warp is geometric, through the depth map the sets share and the path's exact
+    cameras.  A scale-invariant decoder renders depth in units of each camera's near plane; it is brought back to the cameras' units here.
+    Returns {"plain": {...}, "style_0": {...}, ...}, each as `compute_consistency` describes it."""
+    from .inference import gaussian_sets, render_frames
+    from .trajectory import trajectory_cameras
+    sets = gaussian_sets(scene_or_gaussians)
+    if context["image"].shape[0] != 1:
+        raise ValueError("consistency_step scores one scene per call (b == 1)")
+    extrinsics, intrinsics, near, far = trajectory_cameras(context, target, kind, num_frames, None)
+    h, w = context["image"].shape[-2:]
+    color, depth = render_frames(decoder, sets, range(len(sets)), extrinsics, intrinsics, near, far, (h, w), frames_per_pass)
+    if getattr(decoder, "make_scale_invariant", False):
+        depth = depth * near[0, :, None, None].to(depth)
+    scores = metrics.compute_consistency(color, depth, extrinsics[0], intrinsics[0], gaps=gaps, lpips=lpips, depth_tol=depth_tol)
+    return {("plain" if i == 0 else f"style_{i - 1}"): s for i, s in enumerate(scores)}

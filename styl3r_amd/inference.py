@@ -153,6 +153,37 @@ def _panel_set(name, n_sets: int) -> int:
     return i
 
 
+def gaussian_sets(scene_or_gaussians) -> list:
+    """a `StylizedScene`, its list [plain, style 0, ...] of `Gaussians` over one geometry, or one `Gaussians` -> the list"""
+    if isinstance(scene_or_gaussians, StylizedScene):
+        return list(scene_or_gaussians.gaussians)
+    if isinstance(scene_or_gaussians, Gaussians):
+        return [scene_or_gaussians]
+    return list(scene_or_gaussians)
+
+
+def render_frames(decoder, sets: Sequence[Gaussians], used: Sequence[int], extrinsics: Tensor, intrinsics: Tensor, near: Tensor, far: Tensor,
+                  image_shape, frames_per_pass: int = 60):
+    """The float frames of a camera path (b == 1): sets[i] for i in `used` over the geometry of sets[0] through cameras (1,F,...), one
+    `forward_styles` pass per `frames_per_pass` cameras.  Returns (color (len(used),F,3,h,w), depth (F,h,w) the sets share), fp32 on the
+    device.  `render_flythrough` packs them into bytes, `evaluation.consistency_step` scores them."""
+    if frames_per_pass < 1:
+        raise ValueError("render_frames: frames_per_pass >= 1")
+    F = extrinsics.shape[1]
+    h, w = image_shape
+    dev = extrinsics.device
+    color = torch.empty((len(used), F, 3, h, w), dtype=torch.float32, device=dev)
+    depth = torch.empty((F, h, w), dtype=torch.float32, device=dev)
+    with torch.no_grad():
+        for f0 in range(0, F, frames_per_pass):
+            f1 = min(F, f0 + frames_per_pass)
+            out = decoder.forward_styles(sets[0], [sets[i].harmonics for i in used], extrinsics[:, f0:f1], intrinsics[:, f0:f1],
+                                         near[:, f0:f1], far[:, f0:f1], (h, w))
+            color[:, f0:f1] = out.color[:, 0]
+            depth[f0:f1] = out.depth[0]
+    return color, depth
+
+
 def render_flythrough(decoder, scene_or_gaussians: Union[StylizedScene, Gaussians, Sequence[Gaussians]], context: dict,
                       target: Optional[dict] = None, kind: str = "interpolation", num_frames: Optional[int] = None,
                       smooth: Optional[bool] = None, loop_reverse: Optional[bool] = None, panels: Sequence = ("stylized",), axis: int = 0,
@@ -166,12 +197,7 @@ def render_flythrough(decoder, scene_or_gaussians: Union[StylizedScene, Gaussian
     One `gsr_trajectory` launch, one `forward_styles` pass over the sets the panels name per `frames_per_pass` cameras (the rasterizer's
     workspace is sized for one pass, not for the video), `depth_range` over the whole video if a depth panel is asked for, and one
     `pack_frames`.  Nothing is copied to the host."""
-    if isinstance(scene_or_gaussians, StylizedScene):
-        sets = list(scene_or_gaussians.gaussians)
-    elif isinstance(scene_or_gaussians, Gaussians):
-        sets = [scene_or_gaussians]
-    else:
-        sets = list(scene_or_gaussians)
+    sets = gaussian_sets(scene_or_gaussians)
     if context["image"].shape[0] != 1:
         raise ValueError("render_flythrough serves one scene per call (b == 1), as the reference's inference drivers do")
     if not 1 <= len(panels) <= 4 or frames_per_pass < 1:
@@ -179,18 +205,8 @@ def render_flythrough(decoder, scene_or_gaussians: Union[StylizedScene, Gaussian
     which = [_panel_set(p, len(sets)) for p in panels]
     used = sorted({i for i in which if i >= 0}) or [0]
     extrinsics, intrinsics, near, far = trajectory_cameras(context, target, kind, num_frames, smooth)
-    F = extrinsics.shape[1]
     h, w = context["image"].shape[-2:]
-    dev = extrinsics.device
-    color = torch.empty((len(used), F, 3, h, w), dtype=torch.float32, device=dev)
-    depth = torch.empty((F, h, w), dtype=torch.float32, device=dev)
-    with torch.no_grad():
-        for f0 in range(0, F, frames_per_pass):
-            f1 = min(F, f0 + frames_per_pass)
-            out = decoder.forward_styles(sets[0], [sets[i].harmonics for i in used], extrinsics[:, f0:f1], intrinsics[:, f0:f1],
-                                         near[:, f0:f1], far[:, f0:f1], (h, w))
-            color[:, f0:f1] = out.color[:, 0]
-            depth[f0:f1] = out.depth[0]
+    color, depth = render_frames(decoder, sets, used, extrinsics, intrinsics, near, far, (h, w), frames_per_pass)
     tensors = [depth if i < 0 else color[used.index(i)] for i in which]
     rng = depth_range(depth) if -1 in which else None
     return pack_frames(tensors, axis=axis, gap=gap, loop_reverse=KINDS[kind][2] if loop_reverse is None else loop_reverse, depth_range=rng)
