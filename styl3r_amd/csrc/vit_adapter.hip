@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
 struct Adp {   // per-Gaussian intermediates shared by forward and backward

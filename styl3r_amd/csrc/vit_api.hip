@@ -1,89 +1,10 @@
 // vit_api.hip -- the C ABI declared in include/vit_ops.h.
 #include <hip/hip_runtime.h>
 
-#include "../../include/vit_ops.h"
+#include "vit_internal.h"
 
 namespace vit {
 thread_local hipError_t g_last_hip_error = hipSuccess;
-int rope2d(float *tokens, const int64_t *positions, const float *cos_tab, const float *sin_tab, int B, int N, int H,
-           int D, int P, int64_t sb, int64_t sn, int64_t sh, float sign, hipStream_t stream);
-int attention_fwd(const VitAttnArgs &a, const float *q, const float *k, const float *v, float *out, float *lse,
-                  hipStream_t stream);
-int attention_bwd(const VitAttnArgs &a, const float *q, const float *k, const float *v, const float *out, const float *lse,
-                  const float *dout, float *dq, float *dk, float *dv, float *delta_ws, hipStream_t stream);
-int linear_fwd(const float *x, const float *w, const float *bias, const float *residual, float *out, float *pre, int M, int N,
-               int K, int act, hipStream_t stream);
-int split_weight(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream);
-int split_conv_weight_pair(const float *w, void *packed_fwd, void *packed_dx, int Co, int Ci, int ksize, hipStream_t stream);
-int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float *residual, float *out, int B, int Ci, int Co,
-                int H, int W, int ksize, int relu_in, hipStream_t stream);
-int conv_x6_wgrad(const float *dy, const float *in, float *dw, float *dbias, int B, int Ci, int Co, int H, int W, int ksize,
-                  int relu_in, hipStream_t stream);
-int upsample2x_fwd(const float *in, float *out, int64_t planes, int H, int W, hipStream_t stream);
-int relu_dropout_fwd(const float *x, float *y, int64_t n, float p, uint64_t seed, hipStream_t stream);
-int relu_dropout_bwd(const float *y, const float *g, float *dx, int64_t n, float p, hipStream_t stream);
-size_t layernorm_scratch_bytes(int M, int C);
-int layernorm_fwd(const float *x, const float *gamma, const float *beta, float *y, float *mean, float *rstd, int M, int C,
-                  float eps, hipStream_t stream);
-int layernorm_bwd(const float *dy, const float *x, const float *mean, const float *rstd, const float *gamma, const float *dskip,
-                  float *dx, float *dgamma, float *dbeta, float *scratch, int M, int C, int accumulate, hipStream_t stream);
-int upsample2x_bwd(const float *dout, float *din, int64_t planes, int H, int W, hipStream_t stream);
-int upsample2x_add_relu_fwd(const float *in, const float *addend, float *out, int64_t planes, int H, int W, hipStream_t stream);
-int im2col7(const float *img, float *cols, int B, int H, int W, hipStream_t stream);
-int im2col3_rows(const float *in, float *cols, int B, int Ci, int H, int W, int relu, hipStream_t stream);
-int head_tail_fwd(const float *h, const float *w, const float *bias, float *y, int B, int C, int CO, int64_t HW, float p, uint64_t seed,
-                  hipStream_t stream);
-int head_tail_bwd(const float *h, const float *w, const float *dy, float *dh, float *dw, float *db, int B, int C, int CO, int64_t HW, float p,
-                  uint64_t seed, hipStream_t stream);
-int adapter_fwd(const VitAdapterArgs *a, float *means, float *cov, float *sh, float *opac, float *scales, float *rot, hipStream_t s);
-int adapter_bwd(const VitAdapterArgs *a, const float *d_means, const float *d_cov, const float *d_sh, const float *d_opac,
-                float *d_pts0, float *d_ptsr, float *d_par0, float *d_parr, float *d_app, hipStream_t s);
-int linear_x6_wgrad(const float *dy, const float *x, float *dw, float *dbias, int M, int N, int K, int accumulate,
-                    hipStream_t stream);
-int attention_set_arith(int mode);
-int attention_arith();
-size_t x6c_workspace_bytes(int M, int N, int splits);
-int x6c_choose_splits(int M, int N, int K);
-int linear_x6c_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N, int K,
-                   int act, int splits, void *workspace, size_t workspace_bytes, hipStream_t stream);
-int adamw_step(const VitAdamChunk *chunks, int n_chunks, float lr, float beta1, float beta2, float eps, float weight_decay,
-               const float *grad_scale, hipStream_t stream);
-size_t snapshot_chunk_bytes();
-int snapshot_pack(const VitSnapChunk *chunks, int n_chunks, void *staging, VitSnapPartial *partials, hipStream_t stream);
-int x6_set_products(int n);
-int x6_products();
-int x6_set_operand_amax(const void *a, const void *b);
-int x6_set_output_amax(void *word);
-int amax(const float *x, int64_t n, void *out, hipStream_t stream);
-int split_weight_block(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream);
-int split_weight_pair(const float *w, void *packed_f, void *packed_t, int rows, int cols, int block_f, int block_t, hipStream_t stream);
-int split_weights_many(const VitSplitJob *jobs_dev, int njobs, uint32_t total_blocks, hipStream_t stream);
-int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
-                   int K, int act, int cfg, hipStream_t stream);
-size_t lpips_scratch_bytes(const VitLpipsTap *taps, int n_taps, int N);
-size_t lpips_stats_bytes(const VitLpipsTap *taps, int n_taps, int N);
-int lpips_fwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, float *dist, void *scratch, float *stats, hipStream_t stream);
-int lpips_bwd(const VitLpipsTap *taps, int n_taps, int N, int relu_in, const float *g, const float *stats, hipStream_t stream);
-int maxpool2x2_fwd(const float *in, float *out, int64_t planes, int H, int W, hipStream_t stream);
-int maxpool2x2_bwd(const float *in, const float *dout, float *din, int64_t planes, int H, int W, hipStream_t stream);
-int adaattn_stats(const float *q, const float *k, const float *s, const int32_t *index_host, const int32_t *index_dev, int Bq, int Bs, int D,
-                  int C, int Nq, int M, float *mean, float *std, hipStream_t stream);
-size_t adaattn_l1_scratch_bytes(int B, int C);
-int adaattn_l1(const float *p, const float *c, const float *mean, const float *std, int B, int C, int N, void *scratch, float *loss, float *grad,
-               float *cs, hipStream_t stream);
-size_t adain_scratch_bytes(int B, int Bs, int C);
-int adain_fwd(const float *content, const float *style, const int32_t *index_host, const int32_t *index_dev, int B, int Bs, int C, int64_t N,
-              int64_t M, float alpha, float eps, float *out, void *scratch, hipStream_t stream);
-int conv3_rgb_fwd(const float *in, const float *w, const float *bias, const float *scale, const float *shift, float lo, float hi, float *out,
-                  int B, int Ci, int Co, int H, int W, int flags, hipStream_t stream);
-int linear_sm_set(int max_rows, int tm, int nw);
-int linear_sm_ok(int M, int N, int K);
-int linear_sm_grouped(const float *const *x, const void *const *wpb, const float *const *bias, const float *const *residual, float *const *out,
-                      int groups, int M, int N, int K, int act, hipStream_t stream);
-int layernorm_fwd_grouped(const float *const *x, const float *const *gamma, const float *const *beta, float *const *y, int groups, int M, int C,
-                          float eps, hipStream_t stream);
-int linear_x6_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
-                  int K, int act, hipStream_t stream);
 }  // namespace vit
 
 #define VIT_EXPORT extern "C" __attribute__((visibility("default")))

@@ -21,12 +21,10 @@
 
 #include <atomic>
 
-#include "vit_common.h"
+#include "vit_attention_tiles.h"
+#include "vit_internal.h"
 
 namespace vit {
-constexpr int HD = 64;          // head dim
-constexpr int QW = 32;          // queries per wavefront
-constexpr int QB = 128;         // queries per workgroup
 constexpr int KT = 64;          // keys per tile
 constexpr int KSTR = 65;        // LDS row stride of the K tile (floats)
 
@@ -45,30 +43,13 @@ __global__ void __launch_bounds__(256) k_attn_fwd(VitAttnArgs a, const float *__
     const int qi = min(q0 + col, a.Nq - 1);   // clamped: rows beyond Nq compute garbage that is never stored
     const bool wave_active = q0 < a.Nq;       // N = 257 leaves most waves of the last workgroup without queries:
                                               // they only help staging the K/V tiles and skip the MFMA work
-    const float qscale = a.scale * 1.4426950408889634f;   // scores in the base-2 domain
+    const float qscale = a.scale * LOG2E;   // scores in the base-2 domain
 
-    // ---- Q fragment: qf[s] = Q[qi][2s + half], optionally rotated, pre-scaled ----
-    float qf[32];
-    {
-        const float *qr = q + (int64_t)b * a.q_sb + (int64_t)qi * a.q_sn + (int64_t)h * a.q_sh;
+    float qf[32];               // Q fragment, pre-scaled
+    load_frag<ROPE>(qf, q + (int64_t)b * a.q_sb + (int64_t)qi * a.q_sn + (int64_t)h * a.q_sh, half,
+                    ROPE ? a.qpos + ((int64_t)b * a.Nq + qi) * 2 : nullptr, a.cos_tab, a.sin_tab);
 #pragma unroll
-        for (int s = 0; s < 32; ++s) qf[s] = qr[2 * s + half];
-        if (ROPE) {
-            const int64_t py = a.qpos[((int64_t)b * a.Nq + qi) * 2 + 0], px = a.qpos[((int64_t)b * a.Nq + qi) * 2 + 1];
-            // feature d = 2s+half; quarters of 16: pairs (d, d+16) within [0,32) use py, within [32,64) use px
-#pragma unroll
-            for (int s = 0; s < 8; ++s) {
-                const int d = 2 * s + half;   // 0..15
-                const float cy = a.cos_tab[py * 16 + d], sy = a.sin_tab[py * 16 + d];
-                const float cx = a.cos_tab[px * 16 + d], sx = a.sin_tab[px * 16 + d];
-                const float uy = qf[s], vy = qf[s + 8], ux = qf[s + 16], vx = qf[s + 24];
-                qf[s] = uy * cy - vy * sy;      qf[s + 8] = vy * cy + uy * sy;
-                qf[s + 16] = ux * cx - vx * sx; qf[s + 24] = vx * cx + ux * sx;
-            }
-        }
-#pragma unroll
-        for (int s = 0; s < 32; ++s) qf[s] *= qscale;
-    }
+    for (int s = 0; s < 32; ++s) qf[s] *= qscale;
 
     f32x16 o0 = {0}, o1 = {0};          // O^T rows d = rowmap(r) and 32 + rowmap(r), column = this lane's query
     float m = -INFINITY, l = 0.f;
@@ -106,13 +87,7 @@ __global__ void __launch_bounds__(256) k_attn_fwd(VitAttnArgs a, const float *__
             const bool real = k0 + key < a.Nk;     // rows beyond Nk are written as zeros (and masked to -inf below)
             float uy = real ? kreg[it][0] : 0.f, vy = real ? kreg[it][1] : 0.f;
             float ux = real ? kreg[it][2] : 0.f, vx = real ? kreg[it][3] : 0.f;
-            if (ROPE) {
-                const float cy = a.cos_tab[kpy[it] * 16 + dq], sy = a.sin_tab[kpy[it] * 16 + dq];
-                const float cx = a.cos_tab[kpx[it] * 16 + dq], sx = a.sin_tab[kpx[it] * 16 + dq];
-                const float t0 = uy * cy - vy * sy, t1 = vy * cy + uy * sy;
-                const float t2 = ux * cx - vx * sx, t3 = vx * cx + ux * sx;
-                uy = t0; vy = t1; ux = t2; vx = t3;
-            }
+            if (ROPE) rope_quartet(uy, vy, ux, vx, a.cos_tab, a.sin_tab, kpy[it], kpx[it], dq);
             float *dst = s_k + key * KSTR;
             dst[dq] = uy; dst[16 + dq] = vy; dst[32 + dq] = ux; dst[48 + dq] = vx;
             *reinterpret_cast<float4 *>(s_v + key * HD + 4 * dq) = real ? vreg[it] : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -138,34 +113,8 @@ __global__ void __launch_bounds__(256) k_attn_fwd(VitAttnArgs a, const float *__
                 for (int s = 0; s < 32; ++s) st0 = __builtin_amdgcn_mfma_f32_32x32x2f32(ka[2 * s], qf[s], st0, 0, 0, 0);
             }
         }
-        // mask keys beyond Nk: element r of block kb is key k0 + 32 kb + (r&3) + 8 (r>>2) + 4 half
-        if (k0 + KT > a.Nk) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int key = k0 + (r & 3) + 8 * (r >> 2) + 4 * half;
-                if (key >= a.Nk) st0[r] = -INFINITY;
-                if (key + 32 >= a.Nk) st1[r] = -INFINITY;
-            }
-        }
-        // ---- online softmax (base 2) ----
-        float tmax = st0[0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) tmax = fmaxf(tmax, st0[r]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tmax = fmaxf(tmax, st1[r]);
-        tmax = fmaxf(tmax, wave_xor32(tmax));
-        const float m_new = fmaxf(m, tmax);
-        const float alpha = exp2f(m - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st0[r] = exp2f(st0[r] - m_new); psum += st0[r]; }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { st1[r] = exp2f(st1[r] - m_new); psum += st1[r]; }
-        psum += wave_xor32(psum);
-        l = l * alpha + psum;
-        m = m_new;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { o0[r] *= alpha; o1[r] *= alpha; }
+        if (k0 + KT > a.Nk) mask_keys_past(st0, st1, k0, a.Nk, half);
+        online_softmax_step(st0, st1, m, l, o0, o1);
 
         // ---- O^T += V^T P^T : step (kb, r) contracts keys 32 kb + (r&3) + 8 (r>>2) + {0, 4} ----
         {
@@ -188,23 +137,12 @@ __global__ void __launch_bounds__(256) k_attn_fwd(VitAttnArgs a, const float *__
         }
     }
 
-    // ---- epilogue: O = O^T / l, out[q][d], d = 8g + 4 half + {0..3} (+32) ----
+    // ---- epilogue: O = O^T / l ----
     if (q0 + col < a.Nq) {
-        const float inv = 1.f / l;
-        float *orow = out + (int64_t)b * a.o_sb + (int64_t)(q0 + col) * a.o_sn + (int64_t)h * a.o_sh;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d = 8 * g + 4 * half;
-            *reinterpret_cast<float4 *>(orow + d) = make_float4(o0[4 * g] * inv, o0[4 * g + 1] * inv, o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-            *reinterpret_cast<float4 *>(orow + 32 + d) = make_float4(o1[4 * g] * inv, o1[4 * g + 1] * inv, o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-        }
+        store_64(out + (int64_t)b * a.o_sb + (int64_t)(q0 + col) * a.o_sn + (int64_t)h * a.o_sh, o0, o1, half, 1.f / l);
         if (lse && half == 0) lse[((int64_t)b * a.H + h) * a.Nq + q0 + col] = (m + log2f(l)) * 0.6931471805599453f;
     }
 }
-
-int attention_tail_rows(int n_rows, int n_other, int heads_times_batch);
-hipError_t launch_attention_fwd_x6(const VitAttnArgs &a, const float *q, const float *k, const float *v, float *out, float *lse, dim3 grid,
-                                   int products, hipStream_t stream);
 
 // 0: both contractions on the exact-f32 MFMA (this file); 1 (default): bf16x6 split arithmetic on the bf16 MFMA (vit_attention_x6.hip);
 // 2: the same kernels with three partial products per contraction step ("bf16x3": operands good to 2^-18, as vit_x6_set_products(3)).
@@ -218,9 +156,6 @@ int attention_set_arith(int mode)
     return VIT_OK;
 }
 int attention_arith() { return g_attn_arith; }
-int attention_fwd_tail(const VitAttnArgs &a, const float *q, const float *k, const float *v, float *out, float *lse, int rows,
-                       hipStream_t stream);
-int amax(const float *x, int64_t n, void *out, hipStream_t stream);      // vit_gemm_x6.hip
 
 int attention_fwd(const VitAttnArgs &a, const float *q, const float *k, const float *v, float *out, float *lse,
                   hipStream_t stream)
@@ -247,8 +182,7 @@ int attention_fwd(const VitAttnArgs &a, const float *q, const float *k, const fl
         b.amax_out = nullptr;
         const bool contiguous = a.o_sh == HD && a.o_sn == (int64_t)a.H * HD && a.o_sb == (int64_t)a.Nq * a.H * HD;
         if (a.amax_out && !contiguous) return VIT_EINVAL;
-        if (rope) hipLaunchKernelGGL(k_attn_fwd<true>, grid, dim3(256), 0, stream, b, q, k, v, out, lse);
-        else hipLaunchKernelGGL(k_attn_fwd<false>, grid, dim3(256), 0, stream, b, q, k, v, out, lse);
+        for_rope(rope, [&](auto r) { hipLaunchKernelGGL(k_attn_fwd<r.value>, grid, dim3(256), 0, stream, b, q, k, v, out, lse); });
         if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (tail_rows) { const int rc = attention_fwd_tail(b, q, k, v, out, lse, tail_rows, stream); if (rc != VIT_OK) return rc; }
         return a.amax_out ? amax(out, (int64_t)a.B * a.Nq * a.H * HD, a.amax_out, stream) : VIT_OK;

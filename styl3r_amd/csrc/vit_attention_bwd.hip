@@ -17,11 +17,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vit_common.h"
+#include "vit_attention_tiles.h"
+#include "vit_internal.h"
 
 namespace vit {
-constexpr int HD = 64, TSTR = 65, TROWS = 32;
-constexpr float LOG2E = 1.4426950408889634f;
+constexpr int TSTR = 65, TROWS = 32;
 
 // ------------------------------------------------------------------ delta
 __global__ void __launch_bounds__(256) k_attn_delta(const float *__restrict__ o, const float *__restrict__ g, float *__restrict__ delta,
@@ -63,38 +63,10 @@ __device__ inline void stage_rows(float *__restrict__ dst, const float *__restri
         if (gi < n_valid) {
             const float *rp = base + (int64_t)gi * sn;
             uy = rp[dq]; vy = rp[16 + dq]; ux = rp[32 + dq]; vx = rp[48 + dq];
-            if (ROPE) {
-                const int64_t py = pos[(int64_t)gi * 2 + 0], px = pos[(int64_t)gi * 2 + 1];
-                const float cy = cos_tab[py * 16 + dq], sy = sin_tab[py * 16 + dq];
-                const float cx = cos_tab[px * 16 + dq], sx = sin_tab[px * 16 + dq];
-                const float t0 = uy * cy - vy * sy, t1 = vy * cy + uy * sy;
-                const float t2 = ux * cx - vx * sx, t3 = vx * cx + ux * sx;
-                uy = t0; vy = t1; ux = t2; vx = t3;
-            }
+            if (ROPE) rope_quartet(uy, vy, ux, vx, cos_tab, sin_tab, pos[(int64_t)gi * 2 + 0], pos[(int64_t)gi * 2 + 1], dq);
         }
         float *d = dst + row * TSTR;
         d[dq] = uy; d[16 + dq] = vy; d[32 + dq] = ux; d[48 + dq] = vx;
-    }
-}
-
-// load this lane's B-fragment of a row: f[s] = X[row][2s + half], rotated if ROPE
-template <bool ROPE>
-__device__ inline void load_frag(float *f, const float *__restrict__ rp, int half, const int64_t *__restrict__ pos2,
-                                 const float *__restrict__ cos_tab, const float *__restrict__ sin_tab)
-{
-#pragma unroll
-    for (int s = 0; s < 32; ++s) f[s] = rp[2 * s + half];
-    if (ROPE) {
-        const int64_t py = pos2[0], px = pos2[1];
-#pragma unroll
-        for (int s = 0; s < 8; ++s) {
-            const int d = 2 * s + half;
-            const float cy = cos_tab[py * 16 + d], sy = sin_tab[py * 16 + d];
-            const float cx = cos_tab[px * 16 + d], sx = sin_tab[px * 16 + d];
-            const float uy = f[s], vy = f[s + 8], ux = f[s + 16], vx = f[s + 24];
-            f[s] = uy * cy - vy * sy;      f[s + 8] = vy * cy + uy * sy;
-            f[s + 16] = ux * cx - vx * sx; f[s + 24] = vx * cx + ux * sx;
-        }
     }
 }
 
@@ -171,17 +143,9 @@ __global__ void __launch_bounds__(256) k_attn_bwd_kv(VitAttnArgs a, const float 
             const int64_t *pp = a.kpos + ((int64_t)b * a.Nk + key0 + col) * 2;
             unrotate(dk0, dk1, half, pp[0], pp[1], a.cos_tab, a.sin_tab);
         }
-        // dk, dv contiguous (B,Nk,H,64)
-        float *dkr = dk + ((int64_t)b * a.Nk + key0 + col) * (a.dkv_sn ? a.dkv_sn : (int64_t)a.H * HD) + h * HD;
-        float *dvr = dv + ((int64_t)b * a.Nk + key0 + col) * (a.dkv_sn ? a.dkv_sn : (int64_t)a.H * HD) + h * HD;
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int d = 8 * gq + 4 * half;
-            *reinterpret_cast<float4 *>(dkr + d) = make_float4(dk0[4 * gq], dk0[4 * gq + 1], dk0[4 * gq + 2], dk0[4 * gq + 3]);
-            *reinterpret_cast<float4 *>(dkr + 32 + d) = make_float4(dk1[4 * gq], dk1[4 * gq + 1], dk1[4 * gq + 2], dk1[4 * gq + 3]);
-            *reinterpret_cast<float4 *>(dvr + d) = make_float4(dv0[4 * gq], dv0[4 * gq + 1], dv0[4 * gq + 2], dv0[4 * gq + 3]);
-            *reinterpret_cast<float4 *>(dvr + 32 + d) = make_float4(dv1[4 * gq], dv1[4 * gq + 1], dv1[4 * gq + 2], dv1[4 * gq + 3]);
-        }
+        // dk, dv (B,Nk,H,64), token stride dkv_sn
+        store_64(dk + ((int64_t)b * a.Nk + key0 + col) * (a.dkv_sn ? a.dkv_sn : (int64_t)a.H * HD) + h * HD, dk0, dk1, half);
+        store_64(dv + ((int64_t)b * a.Nk + key0 + col) * (a.dkv_sn ? a.dkv_sn : (int64_t)a.H * HD) + h * HD, dv0, dv1, half);
     }
 }
 
@@ -246,24 +210,9 @@ __global__ void __launch_bounds__(256, 3) k_attn_bwd_q(VitAttnArgs a, const floa
             const int64_t *pp = a.qpos + ((int64_t)b * a.Nq + q0 + col) * 2;
             unrotate(dq0, dq1, half, pp[0], pp[1], a.cos_tab, a.sin_tab);
         }
-        float *dqr = dq + ((int64_t)b * a.Nq + q0 + col) * (a.dq_sn ? a.dq_sn : (int64_t)a.H * HD) + h * HD;   // (B,Nq,H,64), token stride dq_sn
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq) {
-            const int d = 8 * gq + 4 * half;
-            *reinterpret_cast<float4 *>(dqr + d) = make_float4(dq0[4 * gq], dq0[4 * gq + 1], dq0[4 * gq + 2], dq0[4 * gq + 3]);
-            *reinterpret_cast<float4 *>(dqr + 32 + d) = make_float4(dq1[4 * gq], dq1[4 * gq + 1], dq1[4 * gq + 2], dq1[4 * gq + 3]);
-        }
+        store_64(dq + ((int64_t)b * a.Nq + q0 + col) * (a.dq_sn ? a.dq_sn : (int64_t)a.H * HD) + h * HD, dq0, dq1, half);   // (B,Nq,H,64), token stride dq_sn
     }
 }
-
-int attention_tail_rows(int n_rows, int n_other, int heads_times_batch);
-int attention_arith();
-hipError_t launch_attention_bwd_x6(const VitAttnArgs &a, const float *q, const float *k, const float *v, const float *dout, const float *lse,
-                                   const float *delta, float *dq, float *dk, float *dv, dim3 gkv, dim3 gq, int products, hipStream_t stream);
-int attention_bwd_tails(const VitAttnArgs &a, const float *q, const float *k, const float *v, const float *lse, const float *dout,
-                        const float *delta, float *dq, float *dk, float *dv, int q_rows, int k_rows, hipStream_t stream);
-
-int amax(const float *x, int64_t n, void *out, hipStream_t stream);      // vit_gemm_x6.hip
 
 int attention_bwd(const VitAttnArgs &a, const float *q, const float *k, const float *v, const float *out, const float *lse,
                   const float *dout, float *dq, float *dk, float *dv, float *delta_ws, hipStream_t stream)
@@ -297,13 +246,10 @@ int attention_bwd(const VitAttnArgs &a, const float *q, const float *k, const fl
                             a.amax_dq && a.amax_dq == a.amax_dk && a.amax_dq == a.amax_dv;
         const bool plain = (a.dq_sn == 0 || a.dq_sn == hd) && (a.dkv_sn == 0 || a.dkv_sn == hd);
         if (want && !packed && !plain) return VIT_EINVAL;
-        if (rope) {
-            hipLaunchKernelGGL(k_attn_bwd_kv<true>, gkv, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dk, dv);
-            hipLaunchKernelGGL(k_attn_bwd_q<true>, gq, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dq);
-        } else {
-            hipLaunchKernelGGL(k_attn_bwd_kv<false>, gkv, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dk, dv);
-            hipLaunchKernelGGL(k_attn_bwd_q<false>, gq, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dq);
-        }
+        for_rope(rope, [&](auto r) {
+            hipLaunchKernelGGL(k_attn_bwd_kv<r.value>, gkv, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dk, dv);
+            hipLaunchKernelGGL(k_attn_bwd_q<r.value>, gq, dim3(256), 0, stream, b, q, k, v, dout, lse, delta_ws, dq);
+        });
         if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (q_tail || k_tail) { const int rc = attention_bwd_tails(b, q, k, v, lse, dout, delta_ws, dq, dk, dv, q_tail, k_tail, stream); if (rc != VIT_OK) return rc; }
         if (!want) return VIT_OK;

@@ -11,34 +11,28 @@
 #include <math.h>
 #include <stdint.h>
 
-#include "vit_common.h"
+#include "vit_attention_tiles.h"
+#include "vit_internal.h"
 
 namespace vit {
 namespace tail {
-constexpr int HD = 64, MAXN = 8192;      // rows of the OTHER operand that fit the score buffer
+constexpr int MAXN = 8192;      // rows of the OTHER operand that fit the score buffer
 
-// rotate one feature of a 64-vector held in LDS (raw[]) by the 2-D position (py, px): returns the rotated feature d
-__device__ inline float rope_feature(const float *raw, int d, int64_t py, int64_t px, const float *cos_tab, const float *sin_tab,
-                                     float sign)
+// rotate one feature of a 64-vector held in LDS (raw[]) by the 2-D position (py, px) (INV: back): returns the rotated feature d
+template <bool INV = false>
+__device__ inline float rope_feature(const float *raw, int d, int64_t py, int64_t px, const float *cos_tab, const float *sin_tab)
 {
     const int g = d >> 4, dq = d & 15;                 // g: 0,1 -> y pair (u, v) ; 2,3 -> x pair
-    const int64_t pos = g < 2 ? py : px;
-    const float c = cos_tab[pos * 16 + dq], s = sign * sin_tab[pos * 16 + dq];
-    const float u = raw[(g & 2) * 16 + dq], v = raw[(g & 2) * 16 + 16 + dq];
-    return (g & 1) ? (v * c + u * s) : (u * c - v * s);
+    float u = raw[(g & 2) * 16 + dq], v = raw[(g & 2) * 16 + 16 + dq];
+    rope_pair<INV>(u, v, cos_tab, sin_tab, g < 2 ? py : px, dq);
+    return (g & 1) ? v : u;
 }
 
 // rotate a whole 64-vector held in registers (x[d]) in place
 __device__ inline void rope_regs(float *x, int64_t py, int64_t px, const float *cos_tab, const float *sin_tab)
 {
 #pragma unroll
-    for (int dq = 0; dq < 16; ++dq) {
-        const float cy = cos_tab[py * 16 + dq], sy = sin_tab[py * 16 + dq];
-        const float cx = cos_tab[px * 16 + dq], sx = sin_tab[px * 16 + dq];
-        const float uy = x[dq], vy = x[16 + dq], ux = x[32 + dq], vx = x[48 + dq];
-        x[dq] = uy * cy - vy * sy; x[16 + dq] = vy * cy + uy * sy;
-        x[32 + dq] = ux * cx - vx * sx; x[48 + dq] = vx * cx + ux * sx;
-    }
+    for (int dq = 0; dq < 16; ++dq) rope_quartet(x[dq], x[16 + dq], x[32 + dq], x[48 + dq], cos_tab, sin_tab, py, px, dq);
 }
 
 __device__ inline float wave_max(float v)
@@ -56,11 +50,11 @@ __global__ void __launch_bounds__(64) k_attn_fwd_tail(VitAttnArgs a, const float
 {
     __shared__ float s_raw[HD], s_q[HD], s_sc[MAXN];
     const int lane = threadIdx.x, h = blockIdx.y, b = blockIdx.z, qi = q_first + blockIdx.x;
-    const float qscale = a.scale * 1.4426950408889634f;
+    const float qscale = a.scale * LOG2E;
     s_raw[lane] = q[(int64_t)b * a.q_sb + (int64_t)qi * a.q_sn + (int64_t)h * a.q_sh + lane];
     __syncthreads();
     float qv = s_raw[lane];
-    if (ROPE) qv = rope_feature(s_raw, lane, a.qpos[((int64_t)b * a.Nq + qi) * 2], a.qpos[((int64_t)b * a.Nq + qi) * 2 + 1], a.cos_tab, a.sin_tab, 1.f);
+    if (ROPE) qv = rope_feature(s_raw, lane, a.qpos[((int64_t)b * a.Nq + qi) * 2], a.qpos[((int64_t)b * a.Nq + qi) * 2 + 1], a.cos_tab, a.sin_tab);
     s_q[lane] = qv * qscale;
     __syncthreads();
     // pass 1: lane = key, scores to LDS
@@ -119,10 +113,10 @@ __global__ void __launch_bounds__(64) k_attn_bwd_q_tail(VitAttnArgs a, const flo
     s_do[lane] = dout[(((int64_t)b * a.Nq + qi) * a.H + h) * HD + lane];
     __syncthreads();
     float qv = s_raw[lane];
-    if (ROPE) qv = rope_feature(s_raw, lane, py, px, a.cos_tab, a.sin_tab, 1.f);
-    s_q[lane] = qv * (a.scale * 1.4426950408889634f);
+    if (ROPE) qv = rope_feature(s_raw, lane, py, px, a.cos_tab, a.sin_tab);
+    s_q[lane] = qv * (a.scale * LOG2E);
     __syncthreads();
-    const float lse2 = lse[((int64_t)b * a.H + h) * a.Nq + qi] * 1.4426950408889634f;
+    const float lse2 = lse[((int64_t)b * a.H + h) * a.Nq + qi] * LOG2E;
     const float del = delta[((int64_t)b * a.H + h) * a.Nq + qi];
     float acc[HD];
 #pragma unroll
@@ -156,7 +150,7 @@ __global__ void __launch_bounds__(64) k_attn_bwd_q_tail(VitAttnArgs a, const flo
     s_raw[lane] = tot;                          // dQ w.r.t. the rotated query
     __syncthreads();
     float r = tot;
-    if (ROPE) r = rope_feature(s_raw, lane, py, px, a.cos_tab, a.sin_tab, -1.f);   // inverse rotation
+    if (ROPE) r = rope_feature<true>(s_raw, lane, py, px, a.cos_tab, a.sin_tab);   // inverse rotation
     dq[((int64_t)b * a.Nq + qi) * (a.dq_sn ? a.dq_sn : (int64_t)a.H * HD) + h * HD + lane] = r;
     if (a.amax_dq) amax_word_fold(a.amax_dq, abs_bits(r));
 }
@@ -175,8 +169,8 @@ __global__ void __launch_bounds__(64) k_attn_bwd_kv_tail(VitAttnArgs a, const fl
     s_v[lane] = v[(int64_t)b * a.v_sb + (int64_t)kj * a.v_sn + (int64_t)h * a.v_sh + lane];
     __syncthreads();
     float kv = s_raw[lane];
-    if (ROPE) kv = rope_feature(s_raw, lane, py, px, a.cos_tab, a.sin_tab, 1.f);
-    s_k[lane] = kv * (a.scale * 1.4426950408889634f);
+    if (ROPE) kv = rope_feature(s_raw, lane, py, px, a.cos_tab, a.sin_tab);
+    s_k[lane] = kv * (a.scale * LOG2E);
     __syncthreads();
     float acck[HD], accv[HD];
 #pragma unroll
@@ -196,7 +190,7 @@ __global__ void __launch_bounds__(64) k_attn_bwd_kv_tail(VitAttnArgs a, const fl
         float sc = 0.f;
 #pragma unroll
         for (int d = 0; d < HD; ++d) sc += qq[d] * s_k[d];
-        const float p = exp2f(sc - lse[((int64_t)b * a.H + h) * a.Nq + i] * 1.4426950408889634f);
+        const float p = exp2f(sc - lse[((int64_t)b * a.H + h) * a.Nq + i] * LOG2E);
         const float ds = p * (dp - delta[((int64_t)b * a.H + h) * a.Nq + i]) * a.scale;
 #pragma unroll
         for (int t = 0; t < 16; ++t) {
@@ -226,7 +220,7 @@ __global__ void __launch_bounds__(64) k_attn_bwd_kv_tail(VitAttnArgs a, const fl
     s_raw[lane] = tk;
     __syncthreads();
     float r = tk;
-    if (ROPE) r = rope_feature(s_raw, lane, py, px, a.cos_tab, a.sin_tab, -1.f);
+    if (ROPE) r = rope_feature<true>(s_raw, lane, py, px, a.cos_tab, a.sin_tab);
     dk[((int64_t)b * a.Nk + kj) * (a.dkv_sn ? a.dkv_sn : (int64_t)a.H * HD) + h * HD + lane] = r;
     if (a.amax_dk) amax_word_fold(a.amax_dk, abs_bits(r));
 }
@@ -247,24 +241,20 @@ int attention_fwd_tail(const VitAttnArgs &a, const float *q, const float *k, con
                        hipStream_t stream)
 {
     const dim3 grid(rows, a.H, a.B);
-    if (a.cos_tab) hipLaunchKernelGGL(tail::k_attn_fwd_tail<true>, grid, dim3(64), 0, stream, a, q, k, v, out, lse, a.Nq - rows);
-    else hipLaunchKernelGGL(tail::k_attn_fwd_tail<false>, grid, dim3(64), 0, stream, a, q, k, v, out, lse, a.Nq - rows);
+    for_rope(a.cos_tab != nullptr, [&](auto r) {
+        hipLaunchKernelGGL(tail::k_attn_fwd_tail<r.value>, grid, dim3(64), 0, stream, a, q, k, v, out, lse, a.Nq - rows);
+    });
     return launch_status();
 }
 int attention_bwd_tails(const VitAttnArgs &a, const float *q, const float *k, const float *v, const float *lse, const float *dout,
                         const float *delta, float *dq, float *dk, float *dv, int q_rows, int k_rows, hipStream_t stream)
 {
-    const bool rope = a.cos_tab != nullptr;
-    if (q_rows) {
-        const dim3 g(q_rows, a.H, a.B);
-        if (rope) hipLaunchKernelGGL(tail::k_attn_bwd_q_tail<true>, g, dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dq, a.Nq - q_rows);
-        else hipLaunchKernelGGL(tail::k_attn_bwd_q_tail<false>, g, dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dq, a.Nq - q_rows);
-    }
-    if (k_rows) {
-        const dim3 g(k_rows, a.H, a.B);
-        if (rope) hipLaunchKernelGGL(tail::k_attn_bwd_kv_tail<true>, g, dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dk, dv, a.Nk - k_rows);
-        else hipLaunchKernelGGL(tail::k_attn_bwd_kv_tail<false>, g, dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dk, dv, a.Nk - k_rows);
-    }
+    for_rope(a.cos_tab != nullptr, [&](auto r) {
+        if (q_rows)
+            hipLaunchKernelGGL(tail::k_attn_bwd_q_tail<r.value>, dim3(q_rows, a.H, a.B), dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dq, a.Nq - q_rows);
+        if (k_rows)
+            hipLaunchKernelGGL(tail::k_attn_bwd_kv_tail<r.value>, dim3(k_rows, a.H, a.B), dim3(64), 0, stream, a, q, k, v, dout, lse, delta, dk, dv, a.Nk - k_rows);
+    });
     return launch_status();
 }
 }  // namespace vit

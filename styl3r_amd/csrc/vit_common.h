@@ -1,6 +1,6 @@
 // vit_common.h -- the device helpers the encoder's kernels (csrc/vit_*.hip) share: vector types, exact GELU, the "bf16x6" / "bf16x3" /
 // "f16x3" split arithmetic (vit_gemm_x6.hip's file header explains bf16x6, the paragraph on f16x3 is below), the |max| word of the f16x3
-// operand scales, the XCD-aware tile walk, RoPE undo, the dropout generator -- and the host-side launch status of the C ABI.
+// operand scales, the XCD-aware tile walk, the accumulator row map, the dropout generator -- and the host-side launch status of the C ABI.
 // One definition each: a tensor split in one kernel gets the same pieces as in every other, and the parity fixtures of tests/golden/
 // were recorded against exactly these functions.
 #pragma once
@@ -224,7 +224,7 @@ __device__ inline void tile_of_block(int bid, int tiles_m, int tiles_n, int &tm,
     tn = in_group / gsz;
 }
 
-// ---- attention -----------------------------------------------------------------------------------------------------------------------------
+// ---- MFMA accumulator layout (the attention tile helpers proper are vit_attention_tiles.h) -----------------------------------------------------------------------------------------------------------------------------
 __device__ inline float wave_xor32(float x)
 {
     // value of lane ^ 32 (the other half-wave of the same query)
@@ -235,22 +235,6 @@ __device__ inline float wave_xor32(float x)
 }
 // row of register r of a 32 x 32 MFMA accumulator in half-wave `half`
 __device__ inline int rowmap(int r, int half) { return (r & 3) + 8 * (r >> 2) + 4 * half; }
-// inverse rotation of a transposed 64 x (lane) gradient held as two f32x16 (rows rowmap(r) and 32 + rowmap(r)):
-// features d < 16 pair with d + 16 -> registers r < 8 pair with r + 8 of the same accumulator.
-__device__ inline void unrotate(f32x16 &lo, f32x16 &hi, int half, int64_t py, int64_t px, const float *__restrict__ cos_tab,
-                                const float *__restrict__ sin_tab)
-{
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const int d = rowmap(r, half);   // 0..15
-        const float cy = cos_tab[py * 16 + d], sy = sin_tab[py * 16 + d];
-        const float cx = cos_tab[px * 16 + d], sx = sin_tab[px * 16 + d];
-        const float gu = lo[r], gv = lo[r + 8];
-        lo[r] = gu * cy + gv * sy; lo[r + 8] = gv * cy - gu * sy;      // transpose of [[c,-s],[s,c]]
-        const float hu = hi[r], hv = hi[r + 8];
-        hi[r] = hu * cx + hv * sx; hi[r + 8] = hv * cx - hu * sx;
-    }
-}
 
 // Philox-4x32-10, the dropout keep mask of the DPT heads keyed by (seed, flat element index / 4): vit_relu_dropout_fwd (vit_resample.hip)
 // and the fused head tail (vit_head_tail.hip) draw the same bits for the same element

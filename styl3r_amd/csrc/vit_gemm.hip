@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
 constexpr int BM = 128, BK = 16, LDT = 132;   // LDT: padded row length of the k-major tiles (BN = 64 * TN)

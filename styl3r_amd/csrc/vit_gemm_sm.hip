@@ -25,12 +25,9 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
-int x6_products();
-void x6_take_amax(const uint32_t *&a, const uint32_t *&b);
-uint32_t *x6_take_output_amax();
-
 namespace sm {
 constexpr int LPAD = 4;          // floats of padding behind a column of the partial tile in LDS (column stride 32 TM + 4: b128 accesses of 8 lanes hit 32 banks)
 

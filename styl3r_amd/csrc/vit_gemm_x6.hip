@@ -27,6 +27,7 @@
 #include <atomic>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
 namespace x6 {

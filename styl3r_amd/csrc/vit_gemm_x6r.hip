@@ -36,12 +36,9 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
-int x6_products();     // vit_gemm_x6.hip: partial products per launch (6 / 3; 2 = "f16x3"), per host thread
-void x6_take_amax(const uint32_t *&a, const uint32_t *&b);      // vit_gemm_x6.hip: the announced |max| words of the next launch (consumed)
-uint32_t *x6_take_output_amax();                                 // vit_gemm_x6.hip: where the next launch publishes the |max| of its output (or null)
-
 namespace x6r {
 constexpr int BK = 16;
 
@@ -772,10 +769,7 @@ int split_weight_block(const float *w, void *packed, int rows, int cols, int tra
 
 // cfg: 1 = ring kernel, 128 x 128 tiles, 3 stages, two workgroups per CU; 2 = ring kernel, 256 x 256 tiles (8 waves);
 // 3 = convert-once ping-pong kernel, 256 x 256 tiles.  (tools/probes/gemm_lab.py sweeps them against vit_linear_x6_fwd.)
-// vit_gemm_sm.hip: the small-M kernel on the block image (cfg 5: no split-K, no zero fill, fused epilogue, |max| word)
-int linear_sm_fwd(const float *x, const void *wpb, const float *bias, const float *residual, float *out, float *pre, int M, int N, int K, int act,
-                  const uint32_t *am_x, const uint32_t *am_w, uint32_t *am_out, hipStream_t stream);
-
+// 5 = linear_sm_fwd (vit_gemm_sm.hip): the small-M kernel on the block image (no split-K, no zero fill, fused epilogue, |max| word)
 int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
                    int K, int act, int cfg, hipStream_t stream)
 {

@@ -17,10 +17,9 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
-uint32_t *x6_take_output_amax();                                 // vit_gemm_x6.hip
-
 namespace {
 constexpr int LN_MAX_N4 = 8;        // C <= 2048
 constexpr int LN_BWD_BLOCKS = 512;  // partial rows of the parameter gradients

@@ -8,6 +8,7 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
 #pragma clang fp contract(off)

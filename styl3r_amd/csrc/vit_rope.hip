@@ -10,10 +10,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vit_common.h"
+#include "vit_attention_tiles.h"
+#include "vit_internal.h"
 
 namespace vit {
-#pragma clang fp contract(off)
 __global__ void __launch_bounds__(256) k_rope2d(float *__restrict__ tokens, const int64_t *__restrict__ pos,
                                                 const float *__restrict__ cos_tab, const float *__restrict__ sin_tab,
                                                 int N, int H, int Q, int P, long long total, int64_t sb, int64_t sn,
@@ -30,14 +30,12 @@ __global__ void __launch_bounds__(256) k_rope2d(float *__restrict__ tokens, cons
         float *t = tokens + b * sb + n * sn + h * sh;
         const float cy = cos_tab[py * Q + d], sy = sign * sin_tab[py * Q + d];
         const float cx = cos_tab[px * Q + d], sx = sign * sin_tab[px * Q + d];
-        const float uy = t[d], vy = t[Q + d], ux = t[2 * Q + d], vx = t[3 * Q + d];
-        t[d] = uy * cy + (-vy) * sy;
-        t[Q + d] = vy * cy + uy * sy;
-        t[2 * Q + d] = ux * cx + (-vx) * sx;
-        t[3 * Q + d] = vx * cx + ux * sx;
+        float uy = t[d], vy = t[Q + d], ux = t[2 * Q + d], vx = t[3 * Q + d];
+        rope_rotate<false>(uy, vy, cy, sy);         // (unfused: see the file header)
+        rope_rotate<false>(ux, vx, cx, sx);
+        t[d] = uy; t[Q + d] = vy; t[2 * Q + d] = ux; t[3 * Q + d] = vx;
     }
 }
-#pragma clang fp contract(fast)
 
 int rope2d(float *tokens, const int64_t *positions, const float *cos_tab, const float *sin_tab, int B, int N, int H,
            int D, int P, int64_t sb, int64_t sn, int64_t sh, float sign, hipStream_t stream)

@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "vit_common.h"
+#include "vit_internal.h"
 
 namespace vit {
 namespace {
