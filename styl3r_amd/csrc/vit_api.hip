@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include "vit_internal.h"
+#include "vit_weight_image.h"
 
 namespace vit {
 thread_local hipError_t g_last_hip_error = hipSuccess;
@@ -39,7 +40,7 @@ VIT_EXPORT int vit_linear_fwd(const float *x, const float *w, const float *bias,
 }
 
 // (+ 8 KiB: the |max| word -- 64 slots, one per cache line -- of the f16x3 mode right behind the pieces, vit_x6_set_products(2))
-VIT_EXPORT size_t vit_split_weight_bytes(int rows, int cols) { return (size_t)rows * (size_t)cols * 6 + 8192; }
+VIT_EXPORT size_t vit_split_weight_bytes(int rows, int cols) { return vit::image::total_bytes(rows, cols, false); }
 
 VIT_EXPORT int vit_split_weight(const float *w, void *packed, int rows, int cols, int transpose, void *stream)
 {
@@ -72,8 +73,7 @@ VIT_EXPORT int vit_amax(const float *x, int64_t n, void *out_word, void *stream)
 
 VIT_EXPORT size_t vit_split_weight_block_bytes(int rows, int cols, int transpose)
 {
-    const size_t R = transpose ? cols : rows, K = transpose ? rows : cols;
-    return ((R + 63) / 64) * 64 * K * 6 + 8192;      // (+ 8 KiB: the weight's |max| word of the f16x3 mode sits right behind the pieces)
+    return vit::image::total_bytes(transpose ? cols : rows, transpose ? rows : cols, true);
 }
 
 VIT_EXPORT int vit_split_weight_block(const float *w, void *packed, int rows, int cols, int transpose, void *stream)

@@ -26,6 +26,7 @@
 
 #include "vit_common.h"
 #include "vit_internal.h"
+#include "vit_weight_image.h"
 
 namespace vit {
 namespace sm {
@@ -309,34 +310,24 @@ static int launch_sm(const sm::SmArgs &a, int groups, hipStream_t stream)
     if (sm::g_force_nw) c.nw = sm::g_force_nw;
     const int tiles = ((M + 32 * c.tm - 1) / (32 * c.tm)) * (N / 64);
     (void)hipGetLastError();
-#define VIT_SM_LAUNCH(TM, NW, NP)                                                                                                                 \
-    do {                                                                                                                                         \
-        auto kern = sm::k_linear_sm<TM, NW, NP>;                                                                                                 \
-        constexpr size_t lds = sm::lds_bytes<TM, NW, NP>();                                                                                      \
-        static bool attr_set = false;    /* (idempotent: a race sets it twice) */                                                               \
-        if (!attr_set && lds > 64 * 1024) {                                                                                                      \
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) { \
-                g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH;                                                                        \
-            }                                                                                                                                    \
-            attr_set = true;                                                                                                                     \
-        }                                                                                                                                        \
-        hipLaunchKernelGGL(kern, dim3(tiles, groups), dim3(NW * 64), lds, stream, a);                                                           \
-    } while (0)
-#define VIT_SM_NP(TM, NW)                                                                                                                         \
-    do {                                                                                                                                         \
-        if (np == 2) VIT_SM_LAUNCH(TM, NW, 2); else if (np == 3) VIT_SM_LAUNCH(TM, NW, 3); else VIT_SM_LAUNCH(TM, NW, 6);                         \
-    } while (0)
-    if (c.tm == 1) { if (c.nw == 8) VIT_SM_NP(1, 8); else VIT_SM_NP(1, 4); }
-    else if (c.nw == 8) { if (np == 2) VIT_SM_LAUNCH(2, 8, 2); else VIT_SM_LAUNCH(2, 8, 3); }
-    else VIT_SM_NP(2, 4);
-#undef VIT_SM_NP
-#undef VIT_SM_LAUNCH
+    int rc = VIT_OK;
+    for_products(np, [&](auto p) { for_flag(c.tm == 2, [&](auto two) { for_flag(c.nw == 8, [&](auto eight) {
+        constexpr int TM = two.value ? 2 : 1, NW = eight.value ? 8 : 4, NP = p.value;
+        if constexpr (!(NP == 6 && TM == 2 && NW == 8)) {      // (not built, see sm::built: linear_sm_ok above refused it)
+            auto kern = sm::k_linear_sm<TM, NW, NP>;
+            constexpr size_t lds = sm::lds_bytes<TM, NW, NP>();
+            static bool attr_set = false;    // (idempotent: a race sets it twice)
+            if (!attr_set && lds > 64 * 1024) {
+                if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+                    g_last_hip_error = hipGetLastError(); rc = VIT_ELAUNCH; return;
+                }
+                attr_set = true;
+            }
+            hipLaunchKernelGGL(kern, dim3(tiles, groups), dim3(NW * 64), lds, stream, a);
+        }
+    }); }); });
+    if (rc != VIT_OK) return rc;
     return launch_status();
-}
-
-static const uint32_t *block_image_amax(const void *wpb, int N, int K)
-{
-    return reinterpret_cast<const uint32_t *>(static_cast<const char *>(wpb) + (size_t)((N + 63) / 64) * 64 * (size_t)K * 6);
 }
 
 // wpb: the BLOCK image of the weight (vit_split_weight_block)
@@ -362,7 +353,7 @@ int linear_sm_grouped(const float *const *x, const void *const *wpb, const float
     for (int g = 0; g < groups; ++g) {
         if (!x[g] || !wpb[g] || !out[g] || (act == 2 && !(residual && residual[g]))) return VIT_EINVAL;
         a.g[g] = sm::SmGroup{x[g], static_cast<const uint4 *>(wpb[g]), bias ? bias[g] : nullptr, residual ? residual[g] : nullptr, out[g], nullptr,
-                             block_image_amax(wpb[g], N, K)};
+                             image::tail_word(wpb[g], N, K, true)};
     }
     if (groups == 1) a.g[1] = a.g[0];
     a.M = M; a.N = N; a.K = K; a.act = act; a.amax_x = ax; a.amax_out = x6_take_output_amax();

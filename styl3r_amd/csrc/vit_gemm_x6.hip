@@ -28,6 +28,7 @@
 
 #include "vit_common.h"
 #include "vit_internal.h"
+#include "vit_weight_image.h"
 
 namespace vit {
 namespace x6 {
@@ -950,104 +951,6 @@ __global__ void __launch_bounds__(256, 2) k_conv_wgrad_x6(const float *__restric
     }
     if (dbias && tn == 0 && co0 + lrow < Co) atomicAdd(dbias + co0 + lrow, bsum);
 }
-
-// w (R, C) row-major fp32 -> packed[r][c/8][piece][8] bf16.  transpose = 0: (r, c) = (row, col) of w, R x C = rows x cols.
-// transpose = 1: packs w^T, i.e. output row r = column r of w, output k index = row of w (tiled through LDS so both the
-// reads and the writes stay coalesced).
-// NPROD == 2 ("f16x3"): two fp16 pieces of w * f16_scale_of(amax_word_read(amax)) in slots 0 / 1 (slot 2 is never read in that mode)
-template <int NPROD>
-__global__ void __launch_bounds__(256) k_split_rows(const float *__restrict__ w, uint4 *__restrict__ packed, int64_t groups,
-                                                    const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail)
-{
-    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one 8-wide k group per thread
-    if (NPROD == 2 && blockIdx.x == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_WORD_STRIDE] = amax[threadIdx.x * AMAX_WORD_STRIDE];      // the line the kernels that read this image take their inverse scale from
-    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;     // (whole waves: before any lane leaves)
-    if (g >= groups) return;
-    const float4 lo = reinterpret_cast<const float4 *>(w)[g * 2], hi = reinterpret_cast<const float4 *>(w)[g * 2 + 1];
-    uint4 q0, q1, q2 = make_uint4(0, 0, 0, 0);
-    split8s<NPROD>(lo, hi, sw, q0, q1, q2);
-    packed[g * 3 + 0] = q0; packed[g * 3 + 1] = q1; if (NPROD != 2) packed[g * 3 + 2] = q2;
-}
-
-template <int NPROD>
-__global__ void __launch_bounds__(256) k_split_transposed(const float *__restrict__ w, uint4 *__restrict__ packed, int rows,
-                                                          int cols, const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail)
-{
-    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_WORD_STRIDE] = amax[threadIdx.x * AMAX_WORD_STRIDE];
-    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;     // (whole waves: before any lane leaves)
-    // tile: 64 source rows (-> k of the output) x 32 source columns (-> output rows)
-    __shared__ float s[64][33];
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 32;
-    for (int i = threadIdx.x; i < 64 * 32; i += 256) {
-        const int r = i >> 5, c = i & 31;
-        s[r][c] = (r0 + r < rows && c0 + c < cols) ? w[(int64_t)(r0 + r) * cols + c0 + c] : 0.f;
-    }
-    __syncthreads();
-    const int c = threadIdx.x >> 3, kg = threadIdx.x & 7;              // 32 output rows x 8 k groups
-    if (c0 + c >= cols || r0 + kg * 8 >= rows) return;
-    float4 lo = make_float4(s[kg * 8 + 0][c], s[kg * 8 + 1][c], s[kg * 8 + 2][c], s[kg * 8 + 3][c]);
-    float4 hi = make_float4(s[kg * 8 + 4][c], s[kg * 8 + 5][c], s[kg * 8 + 6][c], s[kg * 8 + 7][c]);
-    uint4 q0, q1, q2 = make_uint4(0, 0, 0, 0);
-    split8s<NPROD>(lo, hi, sw, q0, q1, q2);
-    uint4 *o = packed + ((int64_t)(c0 + c) * (rows >> 3) + (r0 >> 3) + kg) * 3;
-    o[0] = q0; o[1] = q1; if (NPROD != 2) o[2] = q2;
-}
-
-// Both operand images of a convolution weight w (Co, Ci, k, k) straight from the parameter, in ONE launch (round 6; before: a permute + clone, a
-// flip, a second permute + clone and two k_split_rows launches per weight and optimizer step -- ~290 framework copy launches of a C3 step):
-//   forward image  rows = co, column = tap * Ci + ci               value w[co][ci][tap]                 (vit_conv_x6_fwd's weight)
-//   dX image       rows = ci, column = tap * Co + co               value w[co][ci][k*k - 1 - tap]       (spatially flipped, channel-transposed)
-// both in the row layout of vit_split_weight.  A workgroup owns 16 output channels x 16 input channels x all taps: each of the two images'
-// 8-wide k groups (8 consecutive ci at one (co, tap) / 8 consecutive co at one (ci, tap)) lies inside it.  pdx may be null (forward image only).
-constexpr int CW_T = 16, CW_TAPS_MAX = 9;
-template <int NPROD>
-__global__ void __launch_bounds__(256) k_split_conv_pair(const float *__restrict__ w, uint4 *__restrict__ pf, uint4 *__restrict__ pdx, int Co, int Ci, int kk,
-                                                         const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail_f, uint32_t *__restrict__ tail_dx)
-{
-    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
-        const uint32_t a = amax[threadIdx.x * AMAX_WORD_STRIDE];
-        tail_f[threadIdx.x * AMAX_WORD_STRIDE] = a;
-        if (pdx) tail_dx[threadIdx.x * AMAX_WORD_STRIDE] = a;
-    }
-    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;
-    __shared__ float s[CW_T][CW_T * CW_TAPS_MAX + 1];            // [co][ci * kk + tap]
-    const int co0 = blockIdx.y * CW_T, ci0 = blockIdx.x * CW_T, run = CW_T * kk;
-    for (int i = threadIdx.x; i < CW_T * run; i += 256) {         // per co: CW_T * kk contiguous floats
-        const int co = i / run, e = i - co * run;
-        const int ci = e / kk;
-        s[co][e] = (co0 + co < Co && ci0 + ci < Ci) ? w[((int64_t)(co0 + co) * Ci + ci0) * kk + e] : 0.f;
-    }
-    __syncthreads();
-    const int items = CW_T * kk * (CW_T / 8);
-    {   // forward image
-        const int KG = (kk * Ci) >> 3;
-        for (int i = threadIdx.x; i < items; i += 256) {
-            const int cg = i % (CW_T / 8), t = (i / (CW_T / 8)) % kk, co = i / ((CW_T / 8) * kk);
-            if (co0 + co >= Co || ci0 + cg * 8 >= Ci) continue;
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = s[co][(cg * 8 + j) * kk + t];
-            uint4 q0, q1, q2 = make_uint4(0, 0, 0, 0);
-            split8s<NPROD>(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sw, q0, q1, q2);
-            uint4 *o = pf + ((int64_t)(co0 + co) * KG + ((t * Ci + ci0) >> 3) + cg) * 3;
-            o[0] = q0; o[1] = q1; if (NPROD != 2) o[2] = q2;
-        }
-    }
-    if (pdx) {   // input-gradient image
-        const int KG = (kk * Co) >> 3;
-        for (int i = threadIdx.x; i < items; i += 256) {
-            const int cg = i % (CW_T / 8), t = (i / (CW_T / 8)) % kk, ci = i / ((CW_T / 8) * kk);
-            if (ci0 + ci >= Ci || co0 + cg * 8 >= Co) continue;
-            float v[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) v[j] = s[cg * 8 + j][ci * kk + (kk - 1 - t)];
-            uint4 q0, q1, q2 = make_uint4(0, 0, 0, 0);
-            split8s<NPROD>(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), sw, q0, q1, q2);
-            uint4 *o = pdx + ((int64_t)(ci0 + ci) * KG + ((t * Co + co0) >> 3) + cg) * 3;
-            o[0] = q0; o[1] = q1; if (NPROD != 2) o[2] = q2;
-        }
-    }
-}
 }  // namespace x6
 
 // Partial products per bf16x6 kernel launch: 6 (default, fp32 round-off accuracy) or 3 ("bf16x3": a0 b0 + a0 b1 + a1 b0, operands
@@ -1056,7 +959,7 @@ __global__ void __launch_bounds__(256) k_split_conv_pair(const float *__restrict
 // interleaved with another thread's choice (a serving thread in bf16x3 beside a training thread in bf16x6).
 // n == 2 selects "f16x3": TWO fp16 pieces per operand and the same three products on v_mfma_f32_32x32x16_f16 -- 2^-22 instead of 2^-16
 // per product at the price of bf16x3; every operand tensor then needs its absolute maximum (vit_amax + vit_x6_set_operand_amax for
-// activations; the weight's rides behind its packed image, see split_weight).
+// activations; the weight's rides behind its packed image, see vit_weight_image.h).
 static thread_local int g_x6_products = 6;
 static thread_local const uint32_t *g_amax_a = nullptr, *g_amax_b = nullptr;
 int x6_set_products(int n)
@@ -1079,14 +982,7 @@ static thread_local uint32_t *g_amax_out = nullptr;
 // launch (split-K launches run a vit_amax pass over their result instead).
 int x6_set_output_amax(void *word) { g_amax_out = static_cast<uint32_t *>(word); return VIT_OK; }
 uint32_t *x6_take_output_amax() { uint32_t *p = g_amax_out; g_amax_out = nullptr; return p; }
-static void take_amax(const uint32_t *&a, const uint32_t *&b) { a = g_amax_a; b = g_amax_b; g_amax_a = g_amax_b = nullptr; }
-void x6_take_amax(const uint32_t *&a, const uint32_t *&b) { take_amax(a, b); }      // (vit_gemm_x6r.hip)
-// the weight's |max| word lives right behind its rows x cols x 6 bytes of pieces (vit_split_weight_bytes leaves room)
-static const uint32_t *weight_amax(const void *packed, int rows, int cols)
-{
-    return reinterpret_cast<const uint32_t *>(static_cast<const char *>(packed) + (size_t)rows * (size_t)cols * 6);
-}
-static bool zero_fill(void *p, size_t bytes, hipStream_t stream);
+void x6_take_amax(const uint32_t *&a, const uint32_t *&b) { a = g_amax_a; b = g_amax_b; g_amax_a = g_amax_b = nullptr; }
 int amax(const float *x, int64_t n, void *out, hipStream_t stream)     // *out must be zero before the launch
 {
     if (!x || !out || n <= 0) return VIT_EINVAL;
@@ -1114,55 +1010,7 @@ static int split_count(int tiles, int nslab, int min_slabs)
     return best;
 }
 
-// the two images of a convolution weight (Co, Ci, k, k), k in {1, 3}: see k_split_conv_pair.  packed_dx may be null.  Ci % 8 == 0; with a dX image
-// also Co % 8 == 0.  f16x3: the weight's |max| word must be announced (vit_x6_set_operand_amax(word, NULL)).
-int split_conv_weight_pair(const float *w, void *packed_fwd, void *packed_dx, int Co, int Ci, int ksize, hipStream_t stream)
-{
-    if (!w || !packed_fwd || Co <= 0 || Ci <= 0 || (ksize != 1 && ksize != 3) || (Ci % 8) != 0 || (packed_dx && (Co % 8) != 0)) return VIT_EINVAL;
-    (void)hipGetLastError();
-    const int kk = ksize * ksize;
-    const uint32_t *am, *unused;
-    take_amax(am, unused);
-    uint32_t *tf = const_cast<uint32_t *>(weight_amax(packed_fwd, Co, kk * Ci));
-    uint32_t *td = packed_dx ? const_cast<uint32_t *>(weight_amax(packed_dx, Ci, kk * Co)) : nullptr;
-    const dim3 grid((Ci + x6::CW_T - 1) / x6::CW_T, (Co + x6::CW_T - 1) / x6::CW_T);
-    if (x6_products() == 2) {
-        if (!am) return VIT_EINVAL;
-        hipLaunchKernelGGL(x6::k_split_conv_pair<2>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_fwd), static_cast<uint4 *>(packed_dx), Co, Ci, kk, am, tf, td);
-    } else
-        hipLaunchKernelGGL(x6::k_split_conv_pair<6>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_fwd), static_cast<uint4 *>(packed_dx), Co, Ci, kk, am, tf, td);
-    return launch_status();
-}
-
-int split_weight(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream)
-{
-    if (!w || !packed || rows <= 0 || cols <= 0) return VIT_EINVAL;
-    if ((transpose ? rows : cols) % 8 != 0) return VIT_EINVAL;
-    (void)hipGetLastError();
-    const bool f16 = x6_products() == 2;
-    uint32_t *tail = const_cast<uint32_t *>(weight_amax(packed, rows, cols));
-    // f16x3: the weight's own scale.  The caller may announce the weight's |max| word (vit_x6_set_operand_amax(word, NULL): one vit_amax pass
-    // then serves both images of a weight, forward and transposed); otherwise it is computed here into the word behind the pieces
-    const uint32_t *am, *unused;
-    take_amax(am, unused);
-    if (f16 && !am) {
-        if (!zero_fill(tail, 8192, stream)) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
-        const int rc = amax(w, (int64_t)rows * cols, tail, stream);
-        if (rc != VIT_OK) return rc;
-        am = tail;
-    }
-    if (!transpose) {
-        const int64_t groups = (int64_t)rows * cols / 8;
-        if (f16) hipLaunchKernelGGL(x6::k_split_rows<2>, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), groups, am, tail);
-        else hipLaunchKernelGGL(x6::k_split_rows<6>, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), groups, am, tail);
-    } else {
-        if (f16) hipLaunchKernelGGL(x6::k_split_transposed<2>, dim3((cols + 31) / 32, (rows + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, am, tail);
-        else hipLaunchKernelGGL(x6::k_split_transposed<6>, dim3((cols + 31) / 32, (rows + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, am, tail);
-    }
-    return launch_status();
-}
-
-static bool zero_fill(void *p, size_t bytes, hipStream_t stream)
+bool zero_fill(void *p, size_t bytes, hipStream_t stream)
 {
     const size_t n = bytes / 4;
     if (n == 0) return true;
@@ -1182,8 +1030,8 @@ int linear_x6_fwd(const float *x, const void *wp, const float *bias, const float
     const int tiles = tm * (narrow ? (N + 63) / 64 : (N + 127) / 128);
     const uint4 *w4 = static_cast<const uint4 *>(wp);
     const int np = x6_products();
-    const uint32_t *am_x, *am_unused, *am_w = weight_amax(wp, N, K);
-    take_amax(am_x, am_unused);
+    const uint32_t *am_x, *am_unused, *am_w = image::tail_word(wp, N, K, false);
+    x6_take_amax(am_x, am_unused);
     uint32_t *am_out = x6_take_output_amax();
     if (np == 2 && !am_x) return VIT_EINVAL;      // f16x3 without the activation's |max|: refuse, never guess a scale
     (void)hipGetLastError();
@@ -1195,22 +1043,13 @@ int linear_x6_fwd(const float *x, const void *wp, const float *bias, const float
     }
     if (S > 1) {
         if (!zero_fill(out, (size_t)M * N * sizeof(float), stream)) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
-#define VIT_LAUNCH_X6S(TN, NP) hipLaunchKernelGGL((x6::k_linear_x6<0, TN, true, NP>), dim3(tiles, S), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out)
-        if (np == 3) { if (narrow) VIT_LAUNCH_X6S(1, 3); else VIT_LAUNCH_X6S(2, 3); }
-        else if (np == 2) { if (narrow) VIT_LAUNCH_X6S(1, 2); else VIT_LAUNCH_X6S(2, 2); }
-        else { if (narrow) VIT_LAUNCH_X6S(1, 6); else VIT_LAUNCH_X6S(2, 6); }
-#undef VIT_LAUNCH_X6S
+        for_products(np, [&](auto p) { for_flag(narrow, [&](auto nar) {
+            hipLaunchKernelGGL((x6::k_linear_x6<0, nar.value ? 1 : 2, true, p.value>), dim3(tiles, S), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out);
+        }); });
     } else {
-#define VIT_LAUNCH_X6(ACT, TN)                                                                                                                          \
-    do {                                                                                                                                                \
-        if (np == 3) hipLaunchKernelGGL((x6::k_linear_x6<ACT, TN, false, 3>), dim3(tiles), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out); \
-        else if (np == 2) hipLaunchKernelGGL((x6::k_linear_x6<ACT, TN, false, 2>), dim3(tiles), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out); \
-        else hipLaunchKernelGGL((x6::k_linear_x6<ACT, TN, false, 6>), dim3(tiles), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out);      \
-    } while (0)
-        if (act == 1) { if (narrow) VIT_LAUNCH_X6(1, 1); else VIT_LAUNCH_X6(1, 2); }
-        else if (act == 2) { if (narrow) VIT_LAUNCH_X6(2, 1); else VIT_LAUNCH_X6(2, 2); }
-        else { if (narrow) VIT_LAUNCH_X6(0, 1); else VIT_LAUNCH_X6(0, 2); }
-#undef VIT_LAUNCH_X6
+        for_products(np, [&](auto p) { for_choice3(act, [&](auto a) { for_flag(narrow, [&](auto nar) {
+            hipLaunchKernelGGL((x6::k_linear_x6<a.value, nar.value ? 1 : 2, false, p.value>), dim3(tiles), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out);
+        }); }); });
     }
     if (launch_status() != VIT_OK) return VIT_ELAUNCH;
     if (am_out && S > 1) return amax(out, (int64_t)M * N, am_out, stream);      // split-K partial sums: the |max| of the result needs its own pass
@@ -1249,7 +1088,7 @@ int linear_x6_wgrad(const float *dy, const float *x, float *dw, float *dbias, in
     // split M so that tiles x S fills the 512 resident workgroups (256 CUs x 2) ONCE: 1.1 rounds cost as much as 2
     const int np = x6_products();
     const uint32_t *am_dy, *am_x;
-    take_amax(am_dy, am_x);
+    x6_take_amax(am_dy, am_x);
     if (np == 2 && (!am_dy || !am_x)) return VIT_EINVAL;
     int S = wgrad_splits(tiles, nslab, np == 6 ? 6 : 3);
     { static const char *force = getenv("VIT_WGRAD_S"); if (force) S = atoi(force); }   // (tools/probes/wgrad_lab.py sweeps)
@@ -1263,9 +1102,7 @@ int linear_x6_wgrad(const float *dy, const float *x, float *dw, float *dbias, in
         if (S > 1 && hipMemsetAsync(dw, 0, ((size_t)N * K + (joined ? N : 0)) * sizeof(float), stream) != hipSuccess) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
         if (dbias && !(S > 1 && joined) && hipMemsetAsync(dbias, 0, (size_t)N * sizeof(float), stream) != hipSuccess) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
     }
-    if (np == 3) hipLaunchKernelGGL(x6::k_wgrad_x6<3>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x);
-    else if (np == 2) hipLaunchKernelGGL(x6::k_wgrad_x6<2>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x);
-    else hipLaunchKernelGGL(x6::k_wgrad_x6<6>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x);
+    for_products(np, [&](auto p) { hipLaunchKernelGGL(x6::k_wgrad_x6<p.value>, dim3(tiles, S), dim3(256), 0, stream, dy, x, dw, dbias, M, N, K, accumulate, am_dy, am_x); });
     return launch_status();
 }
 int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float *residual, float *out, int B, int Ci, int Co,
@@ -1284,8 +1121,8 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
     if (tiles > 0x7fffffff) return VIT_EINVAL;
     const uint4 *w4 = static_cast<const uint4 *>(wp);
     const int np = x6_products();
-    const uint32_t *am_in, *am_unused, *am_w = weight_amax(wp, Co, ksize * ksize * Ci);
-    take_amax(am_in, am_unused);
+    const uint32_t *am_in, *am_unused, *am_w = image::tail_word(wp, Co, ksize * ksize * Ci, false);
+    x6_take_amax(am_in, am_unused);
     uint32_t *am_out = x6_take_output_amax();
     if (np == 2 && !am_in) return VIT_EINVAL;
     (void)hipGetLastError();
@@ -1302,16 +1139,9 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
         const int s_cap = (src && W < 32) ? 16 : 8;
         if (ht < 256) { S = (int)(512 / ht); while (S > 1 && nslab / S < 2) --S; if (S < 1) S = 1; if (S > s_cap) S = s_cap; }
         if (S > 1 && !zero_fill(out, (size_t)NP * Co * sizeof(float), stream)) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
-#define VIT_LAUNCH_H6(RL, SRC)                                                                                                                                 \
-    do {                                                                                                                                                        \
-        if (np == 3) hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 3, SRC>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out); \
-        else if (np == 2) hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 2, SRC>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out); \
-        else hipLaunchKernelGGL((x6::k_conv3h_x6<RL, 6, SRC>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out);      \
-    } while (0)
-        if (src == 2) { if (relu_in) VIT_LAUNCH_H6(true, 2); else VIT_LAUNCH_H6(false, 2); }
-        else if (src == 1) { if (relu_in) VIT_LAUNCH_H6(true, 1); else VIT_LAUNCH_H6(false, 1); }
-        else { if (relu_in) VIT_LAUNCH_H6(true, 0); else VIT_LAUNCH_H6(false, 0); }
-#undef VIT_LAUNCH_H6
+        for_products(np, [&](auto p) { for_flag(relu_in, [&](auto relu) { for_choice3(src, [&](auto source) {
+            hipLaunchKernelGGL((x6::k_conv3h_x6<relu.value, p.value, source.value>), dim3((unsigned)ht, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in, am_out);
+        }); }); });
         if (launch_status() != VIT_OK) return VIT_ELAUNCH;
         if (am_out && S > 1) return amax(out, NP * Co, am_out, stream);      // partial sums: the |max| of the result needs its own pass
         return VIT_OK;
@@ -1321,15 +1151,9 @@ int conv_x6_fwd(const float *in, const void *wp, const float *bias, const float 
     const int nslab = ksize * ksize * Ci / x6::BK;
     if (tiles < 256) { S = (int)(512 / tiles); while (S > 1 && nslab / S < 8) --S; if (S < 1) S = 1; if (S > 16) S = 16; }
     if (S > 1 && !zero_fill(out, (size_t)NP * Co * sizeof(float), stream)) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
-#define VIT_LAUNCH_C6(KS, RL)                                                                                                                                   \
-    do {                                                                                                                                                        \
-        if (np == 3) hipLaunchKernelGGL((x6::k_conv_x6<KS, RL, 3>), dim3((unsigned)tiles, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in); \
-        else if (np == 2) hipLaunchKernelGGL((x6::k_conv_x6<KS, RL, 2>), dim3((unsigned)tiles, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in); \
-        else hipLaunchKernelGGL((x6::k_conv_x6<KS, RL, 6>), dim3((unsigned)tiles, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in);      \
-    } while (0)
-    if (ksize == 3) { if (relu_in) VIT_LAUNCH_C6(3, true); else VIT_LAUNCH_C6(3, false); }
-    else { if (relu_in) VIT_LAUNCH_C6(1, true); else VIT_LAUNCH_C6(1, false); }
-#undef VIT_LAUNCH_C6
+    for_products(np, [&](auto p) { for_flag(relu_in, [&](auto relu) { for_flag(ksize == 3, [&](auto three) {
+        hipLaunchKernelGGL((x6::k_conv_x6<three.value ? 3 : 1, relu.value, p.value>), dim3((unsigned)tiles, S), dim3(256), 0, stream, in, w4, bias, residual, out, B, Ci, Co, H, W, gate, am_w, am_in);
+    }); }); });
     if (launch_status() != VIT_OK) return VIT_ELAUNCH;
     if (am_out) return amax(out, NP * Co, am_out, stream);      // (k_conv_x6 does not publish its output's |max| itself: one pass here)
     return VIT_OK;
@@ -1345,20 +1169,14 @@ int conv_x6_wgrad(const float *dy, const float *in, float *dw, float *dbias, int
     int S = split_count(tiles, nslab, 32);   // (r03: 8 / 4 slabs per split measured slower at every DPT shape -- more atomic passes over the tile)
     const int np = x6_products();
     const uint32_t *am_dy, *am_in;
-    take_amax(am_dy, am_in);
+    x6_take_amax(am_dy, am_in);
     if (np == 2 && (!am_dy || !am_in)) return VIT_EINVAL;
     (void)hipGetLastError();
     if (hipMemsetAsync(dw, 0, (size_t)Co * R * sizeof(float), stream) != hipSuccess) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
     if (dbias && hipMemsetAsync(dbias, 0, (size_t)Co * sizeof(float), stream) != hipSuccess) { g_last_hip_error = hipGetLastError(); return VIT_ELAUNCH; }
-#define VIT_LAUNCH_G6(KS, RL)                                                                                                                          \
-    do {                                                                                                                                               \
-        if (np == 3) hipLaunchKernelGGL((x6::k_conv_wgrad_x6<KS, RL, 3>), dim3(tiles, S), dim3(256), 0, stream, dy, in, dw, dbias, B, Ci, Co, H, W, am_dy, am_in);      \
-        else if (np == 2) hipLaunchKernelGGL((x6::k_conv_wgrad_x6<KS, RL, 2>), dim3(tiles, S), dim3(256), 0, stream, dy, in, dw, dbias, B, Ci, Co, H, W, am_dy, am_in);   \
-        else hipLaunchKernelGGL((x6::k_conv_wgrad_x6<KS, RL, 6>), dim3(tiles, S), dim3(256), 0, stream, dy, in, dw, dbias, B, Ci, Co, H, W, am_dy, am_in);            \
-    } while (0)
-    if (ksize == 3) { if (relu_in) VIT_LAUNCH_G6(3, true); else VIT_LAUNCH_G6(3, false); }
-    else { if (relu_in) VIT_LAUNCH_G6(1, true); else VIT_LAUNCH_G6(1, false); }
-#undef VIT_LAUNCH_G6
+    for_products(np, [&](auto p) { for_flag(relu_in, [&](auto relu) { for_flag(ksize == 3, [&](auto three) {
+        hipLaunchKernelGGL((x6::k_conv_wgrad_x6<three.value ? 3 : 1, relu.value, p.value>), dim3(tiles, S), dim3(256), 0, stream, dy, in, dw, dbias, B, Ci, Co, H, W, am_dy, am_in);
+    }); }); });
     return launch_status();
 }
 }  // namespace vit

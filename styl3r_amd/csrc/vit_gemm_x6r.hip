@@ -37,6 +37,7 @@
 
 #include "vit_common.h"
 #include "vit_internal.h"
+#include "vit_weight_image.h"
 
 namespace vit {
 namespace x6r {
@@ -555,217 +556,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 1) k_linear_x6c(const float *__r
     }
 #endif
 }
-
-// w (R, C) row-major fp32 -> block layout packed[r / 64][c / 8][piece][r % 64][8] bf16, rows padded with zeros to a
-// multiple of 64.  transpose = 1 packs w^T (output row = column of w, k = row of w).
-template <int NPROD>
-__global__ void __launch_bounds__(256) k_split_block(const float *__restrict__ w, uint4 *__restrict__ packed, int rows, int cols,
-                                                     int transpose, const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail)
-{
-    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) tail[threadIdx.x * AMAX_WORD_STRIDE] = amax[threadIdx.x * AMAX_WORD_STRIDE];     // the line the readers of this image take their inverse scale from
-    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;
-    // output rows R_ = transpose ? cols : rows, contraction length K_ = transpose ? rows : cols
-    const int R_ = transpose ? cols : rows, K_ = transpose ? rows : cols, KG = K_ >> 3;
-    __shared__ float s[64][65];                       // [output row][k]: 64 rows x 64 k (8 k groups)
-    const int rb = blockIdx.y, k0 = blockIdx.x * 64;
-    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-        int r, k;
-        if (transpose) { k = i >> 6; r = i & 63; } else { r = i >> 6; k = i & 63; }      // coalesced along the source's fast axis
-        const int R = rb * 64 + r, Kx = k0 + k;
-        float v = 0.f;
-        if (R < R_ && Kx < K_) v = transpose ? w[(int64_t)Kx * cols + R] : w[(int64_t)R * cols + Kx];
-        s[r][k] = v;
-    }
-    __syncthreads();
-    // thread -> (k group of the 64-wide slice, output row): consecutive threads = consecutive rows of one plane
-    for (int i = threadIdx.x; i < 8 * 64; i += 256) {
-        const int kg = i >> 6, r = i & 63;
-        if (k0 + kg * 8 >= K_) continue;
-        const float4 lo = make_float4(s[r][kg * 8 + 0], s[r][kg * 8 + 1], s[r][kg * 8 + 2], s[r][kg * 8 + 3]);
-        const float4 hi = make_float4(s[r][kg * 8 + 4], s[r][kg * 8 + 5], s[r][kg * 8 + 6], s[r][kg * 8 + 7]);
-        bf16x8 f0, f1, f2;
-        split8s<NPROD>(lo, hi, sw, f0, f1, f2);
-        uint4 *o = packed + (((int64_t)rb * KG + (k0 >> 3) + kg) * 3) * 64 + r;
-        o[0] = __builtin_bit_cast(uint4, f0); o[64] = __builtin_bit_cast(uint4, f1); if (NPROD != 2) o[128] = __builtin_bit_cast(uint4, f2);
-    }
-}
-// BOTH images of one Linear weight in one launch (round 6): the forward image (output rows = rows of w, contraction along its columns) and
-// the transposed one for the input-gradient GEMM (output rows = columns of w), each in the block layout above (flag set) or in the
-// MFMA-order row layout of vit_split_weight (packed[row][k / 8][piece][8]).  After an optimizer step every trainable weight needs both
-// again; one launch per image read the fp32 weight twice and was ~1 270 launches / 12 ms of a 281 ms C3 step, launch-bound.  A workgroup owns
-// a 64 x 64 tile of w: it IS a 64-row x 64-k tile of the forward image and a 64-row x 64-k tile of the transposed one.  Same split
-// function on the same values: the bytes equal the single-image kernels' (tests/test_gpu_vit.py compares them).
-template <int NPROD>
-__global__ void __launch_bounds__(256) k_split_pair(const float *__restrict__ w, uint4 *__restrict__ pf, uint4 *__restrict__ pt, int rows, int cols,
-                                                    int block_f, int block_t, const uint32_t *__restrict__ amax, uint32_t *__restrict__ tail_f,
-                                                    uint32_t *__restrict__ tail_t)
-{
-    if (NPROD == 2 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 64) {
-        const uint32_t a = amax[threadIdx.x * AMAX_WORD_STRIDE];
-        tail_f[threadIdx.x * AMAX_WORD_STRIDE] = a; tail_t[threadIdx.x * AMAX_WORD_STRIDE] = a;
-    }
-    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(amax)) : 1.f;
-    __shared__ float s[64][65];                       // [row of w][column of w]
-    const int r0 = blockIdx.y * 64, c0 = blockIdx.x * 64;
-    if ((cols & 3) == 0) {                            // four columns per load (rows of w are 16-byte aligned)
-        for (int i = threadIdx.x; i < 64 * 16; i += 256) {
-            const int r = i >> 4, c4 = (i & 15) * 4;
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (r0 + r < rows && c0 + c4 < cols) v = *reinterpret_cast<const float4 *>(w + (int64_t)(r0 + r) * cols + c0 + c4);
-            s[r][c4] = v.x; s[r][c4 + 1] = v.y; s[r][c4 + 2] = v.z; s[r][c4 + 3] = v.w;
-        }
-    } else {
-        for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-            const int r = i >> 6, c = i & 63;
-            s[r][c] = (r0 + r < rows && c0 + c < cols) ? w[(int64_t)(r0 + r) * cols + c0 + c] : 0.f;
-        }
-    }
-    __syncthreads();
-    // ---- forward image: output row = row of w, k = column of w ----
-    {
-        const int KG = cols >> 3;
-        for (int i = threadIdx.x; i < 8 * 64; i += 256) {
-            const int kg = block_f ? (i >> 6) : (i & 7), r = block_f ? (i & 63) : (i >> 3);
-            if (c0 + kg * 8 >= cols) continue;
-            const float4 lo = make_float4(s[r][kg * 8 + 0], s[r][kg * 8 + 1], s[r][kg * 8 + 2], s[r][kg * 8 + 3]);
-            const float4 hi = make_float4(s[r][kg * 8 + 4], s[r][kg * 8 + 5], s[r][kg * 8 + 6], s[r][kg * 8 + 7]);
-            bf16x8 f0, f1, f2;
-            split8s<NPROD>(lo, hi, sw, f0, f1, f2);
-            if (block_f) {
-                uint4 *o = pf + (((int64_t)blockIdx.y * KG + (c0 >> 3) + kg) * 3) * 64 + r;
-                o[0] = __builtin_bit_cast(uint4, f0); o[64] = __builtin_bit_cast(uint4, f1); if (NPROD != 2) o[128] = __builtin_bit_cast(uint4, f2);
-            } else if (r0 + r < rows) {
-                uint4 *o = pf + ((int64_t)(r0 + r) * KG + (c0 >> 3) + kg) * 3;
-                o[0] = __builtin_bit_cast(uint4, f0); o[1] = __builtin_bit_cast(uint4, f1); if (NPROD != 2) o[2] = __builtin_bit_cast(uint4, f2);
-            }
-        }
-    }
-    // ---- transposed image: output row = column of w, k = row of w ----
-    {
-        const int KG = rows >> 3;
-        for (int i = threadIdx.x; i < 8 * 64; i += 256) {
-            const int rg = block_t ? (i >> 6) : (i & 7), c = block_t ? (i & 63) : (i >> 3);
-            if (r0 + rg * 8 >= rows) continue;
-            const float4 lo = make_float4(s[rg * 8 + 0][c], s[rg * 8 + 1][c], s[rg * 8 + 2][c], s[rg * 8 + 3][c]);
-            const float4 hi = make_float4(s[rg * 8 + 4][c], s[rg * 8 + 5][c], s[rg * 8 + 6][c], s[rg * 8 + 7][c]);
-            bf16x8 f0, f1, f2;
-            split8s<NPROD>(lo, hi, sw, f0, f1, f2);
-            if (block_t) {
-                uint4 *o = pt + (((int64_t)blockIdx.x * KG + (r0 >> 3) + rg) * 3) * 64 + c;
-                o[0] = __builtin_bit_cast(uint4, f0); o[64] = __builtin_bit_cast(uint4, f1); if (NPROD != 2) o[128] = __builtin_bit_cast(uint4, f2);
-            } else if (c0 + c < cols) {
-                uint4 *o = pt + ((int64_t)(c0 + c) * KG + (r0 >> 3) + rg) * 3;
-                o[0] = __builtin_bit_cast(uint4, f0); o[1] = __builtin_bit_cast(uint4, f1); if (NPROD != 2) o[2] = __builtin_bit_cast(uint4, f2);
-            }
-        }
-    }
-}
-
-// All the weight images of a model in ONE launch (after an optimizer step every weight changed: the per-weight launches above were
-// 1 274 launches and 12 ms of a 285 ms train step at 1.4 TB/s -- launch-bound).  A job = one image of one weight; a workgroup = one
-// 64-row x 64-k tile of one job (binary search over the jobs' first-block table), staged through LDS exactly as k_split_block does, then
-// written in the job's layout: kind bit 1 = the BLOCK layout above, else the MFMA-order layout of vit_split_weight
-// (packed[row][k / 8][piece][8]); kind bit 0 = pack w^T.  Same bytes as the single-weight kernels (tests/test_gpu_vit.py compares them).
-template <int NPROD>
-__global__ void __launch_bounds__(256) k_split_many(const VitSplitJob *__restrict__ jobs, int njobs)
-{
-    int lo = 0, hi = njobs - 1;                        // last job whose first_block <= blockIdx.x
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (jobs[mid].first_block <= blockIdx.x) lo = mid; else hi = mid - 1;
-    }
-    const VitSplitJob jb = jobs[lo];
-    const uint32_t local = blockIdx.x - jb.first_block;
-    const int bx = (int)(local % jb.nbx), rb = (int)(local / jb.nbx);
-    const int rows = jb.rows, cols = jb.cols, transpose = jb.kind & 1, block = jb.kind & 2;
-    const float *__restrict__ w = jb.w;
-    uint4 *__restrict__ packed = static_cast<uint4 *>(jb.packed);
-    if (NPROD == 2 && local == 0 && threadIdx.x < 64) jb.tail[threadIdx.x * AMAX_WORD_STRIDE] = jb.amax[threadIdx.x * AMAX_WORD_STRIDE];
-    const float sw = NPROD == 2 ? f16_scale_of(amax_word_read(jb.amax)) : 1.f;
-    const int R_ = transpose ? cols : rows, K_ = transpose ? rows : cols, KG = K_ >> 3;
-    __shared__ float s[64][65];
-    const int k0 = bx * 64;
-    for (int i = threadIdx.x; i < 64 * 64; i += 256) {
-        int r, k;
-        if (transpose) { k = i >> 6; r = i & 63; } else { r = i >> 6; k = i & 63; }
-        const int R = rb * 64 + r, Kx = k0 + k;
-        float v = 0.f;
-        if (R < R_ && Kx < K_) v = transpose ? w[(int64_t)Kx * cols + R] : w[(int64_t)R * cols + Kx];
-        s[r][k] = v;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < 8 * 64; i += 256) {
-        // block layout: consecutive threads = consecutive rows of one (k group, piece) plane; row-major layout: consecutive threads =
-        // consecutive k groups of one row (48 contiguous bytes each)
-        const int kg = block ? (i >> 6) : (i & 7), r = block ? (i & 63) : (i >> 3);
-        if (k0 + kg * 8 >= K_) continue;
-        const float4 lo4 = make_float4(s[r][kg * 8 + 0], s[r][kg * 8 + 1], s[r][kg * 8 + 2], s[r][kg * 8 + 3]);
-        const float4 hi4 = make_float4(s[r][kg * 8 + 4], s[r][kg * 8 + 5], s[r][kg * 8 + 6], s[r][kg * 8 + 7]);
-        bf16x8 f0, f1, f2;
-        split8s<NPROD>(lo4, hi4, sw, f0, f1, f2);
-        if (block) {
-            uint4 *o = packed + (((int64_t)rb * KG + (k0 >> 3) + kg) * 3) * 64 + r;
-            o[0] = __builtin_bit_cast(uint4, f0); o[64] = __builtin_bit_cast(uint4, f1); if (NPROD != 2) o[128] = __builtin_bit_cast(uint4, f2);
-        } else if (rb * 64 + r < R_) {
-            uint4 *o = packed + ((int64_t)(rb * 64 + r) * KG + (k0 >> 3) + kg) * 3;
-            o[0] = __builtin_bit_cast(uint4, f0); o[1] = __builtin_bit_cast(uint4, f1);
-            if (NPROD != 2) o[2] = __builtin_bit_cast(uint4, f2);      // (f16x3 never reads slot 2)
-        }
-    }
-}
 }  // namespace x6r
-
-int split_weights_many(const VitSplitJob *jobs_dev, int njobs, uint32_t total_blocks, hipStream_t stream)
-{
-    if (!jobs_dev || njobs <= 0 || total_blocks == 0) return VIT_EINVAL;
-    (void)hipGetLastError();
-    const int np = x6_products();
-    if (np == 2) hipLaunchKernelGGL(x6r::k_split_many<2>, dim3(total_blocks), dim3(256), 0, stream, jobs_dev, njobs);
-    else if (np == 3) hipLaunchKernelGGL(x6r::k_split_many<3>, dim3(total_blocks), dim3(256), 0, stream, jobs_dev, njobs);
-    else hipLaunchKernelGGL(x6r::k_split_many<6>, dim3(total_blocks), dim3(256), 0, stream, jobs_dev, njobs);
-    return launch_status();
-}
-
-// both images of a Linear weight (rows x cols) in one launch: see k_split_pair.  block_f / block_t: the block layout (1) or the row layout (0)
-// of the forward / the transposed image; sizes as vit_split_weight_block_bytes / vit_split_weight_bytes say.
-int split_weight_pair(const float *w, void *packed_f, void *packed_t, int rows, int cols, int block_f, int block_t, hipStream_t stream)
-{
-    if (!w || !packed_f || !packed_t || rows <= 0 || cols <= 0 || (rows % 8) != 0 || (cols % 8) != 0) return VIT_EINVAL;
-    (void)hipGetLastError();
-    const uint32_t *am, *unused;
-    x6_take_amax(am, unused);
-    auto tail_of = [](void *p, int R_, int K_, int block) {
-        const size_t pieces = block ? (size_t)((R_ + 63) / 64) * 64 * (size_t)K_ * 6 : (size_t)R_ * (size_t)K_ * 6;
-        return reinterpret_cast<uint32_t *>(static_cast<char *>(p) + pieces);
-    };
-    uint32_t *tf = tail_of(packed_f, rows, cols, block_f), *tt = tail_of(packed_t, cols, rows, block_t);
-    const dim3 grid((cols + 63) / 64, (rows + 63) / 64);
-    const int np = x6_products();
-    if (np == 2) {
-        if (!am) return VIT_EINVAL;        // f16x3: the weight's |max| word must be announced (vit_x6_set_operand_amax(word, NULL))
-        hipLaunchKernelGGL(x6r::k_split_pair<2>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_f), static_cast<uint4 *>(packed_t), rows, cols, block_f, block_t, am, tf, tt);
-    } else
-        hipLaunchKernelGGL(x6r::k_split_pair<6>, grid, dim3(256), 0, stream, w, static_cast<uint4 *>(packed_f), static_cast<uint4 *>(packed_t), rows, cols, block_f, block_t, am, tf, tt);
-    return launch_status();
-}
-
-int split_weight_block(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream)
-{
-    if (!w || !packed || rows <= 0 || cols <= 0) return VIT_EINVAL;
-    const int R_ = transpose ? cols : rows, K_ = transpose ? rows : cols;
-    if (K_ % 8 != 0) return VIT_EINVAL;
-    (void)hipGetLastError();
-    // f16x3: the weight's |max| word must be announced (vit_x6_set_operand_amax(word, NULL)); the image keeps a copy right behind its pieces
-    const uint32_t *am, *unused;
-    x6_take_amax(am, unused);
-    uint32_t *tail = reinterpret_cast<uint32_t *>(static_cast<char *>(packed) + (size_t)((R_ + 63) / 64) * 64 * (size_t)K_ * 6);
-    if (x6_products() == 2) {
-        if (!am) return VIT_EINVAL;
-        hipLaunchKernelGGL(x6r::k_split_block<2>, dim3((K_ + 63) / 64, (R_ + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, transpose, am, tail);
-    } else
-        hipLaunchKernelGGL(x6r::k_split_block<6>, dim3((K_ + 63) / 64, (R_ + 63) / 64), dim3(256), 0, stream, w, static_cast<uint4 *>(packed), rows, cols, transpose, am, tail);
-    return launch_status();
-}
 
 // cfg: 1 = ring kernel, 128 x 128 tiles, 3 stages, two workgroups per CU; 2 = ring kernel, 256 x 256 tiles (8 waves);
 // 3 = convert-once ping-pong kernel, 256 x 256 tiles.  (tools/probes/gemm_lab.py sweeps them against vit_linear_x6_fwd.)
@@ -778,57 +569,40 @@ int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const floa
         if (M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 2 || (act == 2 && (!residual || pre))) return VIT_EINVAL;
         const uint32_t *ax, *unused;
         x6_take_amax(ax, unused);
-        const uint32_t *aw = reinterpret_cast<const uint32_t *>(static_cast<const char *>(wp) + (size_t)((N + 63) / 64) * 64 * (size_t)K * 6);
-        return linear_sm_fwd(x, wp, bias, residual, out, pre, M, N, K, act, ax, aw, x6_take_output_amax(), stream);
+        return linear_sm_fwd(x, wp, bias, residual, out, pre, M, N, K, act, ax, image::tail_word(wp, N, K, true), x6_take_output_amax(), stream);
     }
     if (M <= 0 || N <= 0 || K <= 0 || (K % x6r::BK) != 0 || act < 0 || act > 2 || (act == 2 && (!residual || pre || (cfg != 1 && cfg != 3))) ||
         !((cfg >= 1 && cfg <= 4) || (cfg >= 34 && cfg <= 40))) return VIT_EINVAL;   // 32 + S: cfg 3 with an S-way K split; act 2: see vit_linear_x6_fwd
     const uint4 *w4 = static_cast<const uint4 *>(wp);
     const uint32_t *am_x, *am_unused;
     x6_take_amax(am_x, am_unused);
-    const uint32_t *am_w = reinterpret_cast<const uint32_t *>(static_cast<const char *>(wp) + (size_t)((N + 63) / 64) * 64 * (size_t)K * 6);
+    const uint32_t *am_w = image::tail_word(wp, N, K, true);
     const bool f16 = x6_products() == 2;
     uint32_t *am_out = x6_take_output_amax();
     if (am_out && cfg != 1 && cfg != 3) return VIT_EINVAL;   // the lockstep 256 x 256 kernel (cfg 2) does not publish its output's |max|
     if (f16 && ((cfg != 1 && cfg != 3) || !am_x)) return VIT_EINVAL;      // f16x3: cfg 1 / cfg 3, with the activation's |max| announced
     (void)hipGetLastError();
-#define X6R_ARGS(BM, BN, THREADS) dim3(((M + BM - 1) / BM) * ((N + BN - 1) / BN)), dim3(THREADS), 0, stream, x, w4, bias, residual, out, pre, M, N, K
-    const bool three = x6_products() == 3;
+    const int np = x6_products();
+    auto tiles = [&](int bm, int bn) { return dim3(((M + bm - 1) / bm) * ((N + bn - 1) / bn)); };
     if (cfg == 1) {
-        if (f16) {
-            if (act == 2) hipLaunchKernelGGL((x6r::k_linear_x6r<2, 128, 128, 2, 2, 3, 2, 2>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-            else if (act) hipLaunchKernelGGL((x6r::k_linear_x6r<1, 128, 128, 2, 2, 3, 2, 2>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-            else hipLaunchKernelGGL((x6r::k_linear_x6r<0, 128, 128, 2, 2, 3, 2, 2>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-        } else if (three) {
-            if (act == 2) hipLaunchKernelGGL((x6r::k_linear_x6r<2, 128, 128, 2, 2, 3, 2, 3>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-            else if (act) hipLaunchKernelGGL((x6r::k_linear_x6r<1, 128, 128, 2, 2, 3, 2, 3>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-            else hipLaunchKernelGGL((x6r::k_linear_x6r<0, 128, 128, 2, 2, 3, 2, 3>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-        } else if (act == 2) hipLaunchKernelGGL((x6r::k_linear_x6r<2, 128, 128, 2, 2, 3, 2>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-        else if (act) hipLaunchKernelGGL((x6r::k_linear_x6r<1, 128, 128, 2, 2, 3, 2>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-        else hipLaunchKernelGGL((x6r::k_linear_x6r<0, 128, 128, 2, 2, 3, 2>), X6R_ARGS(128, 128, 256), am_x, am_w, am_out);
-    } else if (cfg == 2) {
+        for_products(np, [&](auto p) { for_choice3(act, [&](auto a) {
+            hipLaunchKernelGGL((x6r::k_linear_x6r<a.value, 128, 128, 2, 2, 3, 2, p.value>), tiles(128, 128), dim3(256), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out);
+        }); });
+    } else if (cfg == 2) {      // built with six products and act 0 / 1 only: a bf16x3 thread runs the six-product kernel too
         if (act == 2) return VIT_EINVAL;
-        if (act) hipLaunchKernelGGL((x6r::k_linear_x6r<1, 256, 256, 2, 4, 3, 1>), X6R_ARGS(256, 256, 512), am_x, am_w, am_out);
-        else hipLaunchKernelGGL((x6r::k_linear_x6r<0, 256, 256, 2, 4, 3, 1>), X6R_ARGS(256, 256, 512), am_x, am_w, am_out);
+        for_flag(act == 1, [&](auto gelu) {
+            hipLaunchKernelGGL((x6r::k_linear_x6r<gelu.value ? 1 : 0, 256, 256, 2, 4, 3, 1>), tiles(256, 256), dim3(512), 0, stream, x, w4, bias, residual, out, pre, M, N, K, am_x, am_w, am_out);
+        });
     } else if (cfg == 4) {      // phase-timing instantiation (tools/probes/gemm_lab.py): needs `pre` with room for 32 floats
         if (!pre || (size_t)M * N < 32) return VIT_EINVAL;
-        hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4, true>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
+        hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4, true>), tiles(256, 256), dim3(512), 0, stream, x, w4, bias, residual, out, pre, M, N, K, nullptr, nullptr, am_x, am_w, am_out);
     } else if (cfg >= 34) {
         return VIT_EINVAL;            // K splits need a workspace: vit_linear_x6c_fwd
-    } else if (f16) {
-        if (act == 2) hipLaunchKernelGGL((x6r::k_linear_x6c<2, 256, 256, 2, 4, false, 2>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-        else if (act) hipLaunchKernelGGL((x6r::k_linear_x6c<1, 256, 256, 2, 4, false, 2>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-        else hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4, false, 2>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-    } else if (three) {
-        if (act == 2) hipLaunchKernelGGL((x6r::k_linear_x6c<2, 256, 256, 2, 4, false, 3>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-        else if (act) hipLaunchKernelGGL((x6r::k_linear_x6c<1, 256, 256, 2, 4, false, 3>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-        else hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4, false, 3>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
     } else {
-        if (act == 2) hipLaunchKernelGGL((x6r::k_linear_x6c<2, 256, 256, 2, 4>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-        else if (act) hipLaunchKernelGGL((x6r::k_linear_x6c<1, 256, 256, 2, 4>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
-        else hipLaunchKernelGGL((x6r::k_linear_x6c<0, 256, 256, 2, 4>), X6R_ARGS(256, 256, 512), nullptr, nullptr, am_x, am_w, am_out);
+        for_products(np, [&](auto p) { for_choice3(act, [&](auto a) {
+            hipLaunchKernelGGL((x6r::k_linear_x6c<a.value, 256, 256, 2, 4, false, p.value>), tiles(256, 256), dim3(512), 0, stream, x, w4, bias, residual, out, pre, M, N, K, nullptr, nullptr, am_x, am_w, am_out);
+        }); });
     }
-#undef X6R_ARGS
     return launch_status();
 }
 

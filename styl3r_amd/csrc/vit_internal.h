@@ -12,19 +12,31 @@
 
 namespace vit {
 // ---- template instantiations picked at run time ----------------------------------------------------------------------------------------------
-// f(std::bool_constant<rope>) / f(std::bool_constant<rope>, std::integral_constant<int, NP>): the kernels' <ROPE> and <ROPE, NP> parameters from
-// the launch's values; NP = the partial products per contraction step, 6 ("bf16x6"), 3 ("bf16x3") or 2 ("f16x3")
-template <typename F> inline void for_rope(bool rope, F &&f)
+// A launcher hands its run-time values to a generic lambda as constants and names the kernel's template arguments from them:
+//   for_flag      f(std::bool_constant<flag>)                  a bool parameter (<ROPE>, <RELU>, a narrow tile, ...)
+//   for_products  f(std::integral_constant<int, NP>)           NP = the partial products per contraction step: 6 ("bf16x6"), 3 ("bf16x3"), 2 ("f16x3")
+//   for_choice3   f(std::integral_constant<int, V>)            a parameter that is 0, 1 or 2: the Linear epilogue (none / GELU / GELU' gate), the halo convolution's source mode
+// Every path through a lambda is instantiated: where a family deliberately builds fewer kernels, its lambda says so with `if constexpr`.
+template <typename F> inline void for_flag(bool flag, F &&f)
 {
-    if (rope) f(std::true_type{}); else f(std::false_type{});
+    if (flag) f(std::true_type{}); else f(std::false_type{});
 }
+template <typename F> inline void for_products(int products, F &&f)
+{
+    if (products == 2) f(std::integral_constant<int, 2>{});
+    else if (products == 3) f(std::integral_constant<int, 3>{});
+    else f(std::integral_constant<int, 6>{});
+}
+template <typename F> inline void for_choice3(int v, F &&f)
+{
+    if (v == 1) f(std::integral_constant<int, 1>{});
+    else if (v == 2) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 0>{});
+}
+template <typename F> inline void for_rope(bool rope, F &&f) { for_flag(rope, f); }
 template <typename F> inline void for_rope_products(bool rope, int products, F &&f)
 {
-    for_rope(rope, [&](auto r) {
-        if (products == 2) f(r, std::integral_constant<int, 2>{});
-        else if (products == 3) f(r, std::integral_constant<int, 3>{});
-        else f(r, std::integral_constant<int, 6>{});
-    });
+    for_flag(rope, [&](auto r) { for_products(products, [&](auto np) { f(r, np); }); });
 }
 
 // ---- vit_rope.hip ----
@@ -60,8 +72,7 @@ int x6_set_output_amax(void *word);
 void x6_take_amax(const uint32_t *&a, const uint32_t *&b);      // the announced |max| words of the next launch (consumed)
 uint32_t *x6_take_output_amax();                                 // where the next launch publishes the |max| of its output (or null)
 int amax(const float *x, int64_t n, void *out, hipStream_t stream);
-int split_weight(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream);
-int split_conv_weight_pair(const float *w, void *packed_fwd, void *packed_dx, int Co, int Ci, int ksize, hipStream_t stream);
+bool zero_fill(void *p, size_t bytes, hipStream_t stream);      // a kernel, not hipMemsetAsync: replays faithfully from a captured graph
 int linear_x6_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
                   int K, int act, hipStream_t stream);
 int linear_x6_wgrad(const float *dy, const float *x, float *dw, float *dbias, int M, int N, int K, int accumulate,
@@ -76,11 +87,15 @@ size_t x6c_workspace_bytes(int M, int N, int splits);
 int x6c_choose_splits(int M, int N, int K);
 int linear_x6c_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N, int K,
                    int act, int splits, void *workspace, size_t workspace_bytes, hipStream_t stream);
+int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
+                   int K, int act, int cfg, hipStream_t stream);
+
+// ---- vit_weight_image.hip: the packed weight images the kernels above read (layout: vit_weight_image.h) ----
+int split_weight(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream);
 int split_weight_block(const float *w, void *packed, int rows, int cols, int transpose, hipStream_t stream);
 int split_weight_pair(const float *w, void *packed_f, void *packed_t, int rows, int cols, int block_f, int block_t, hipStream_t stream);
 int split_weights_many(const VitSplitJob *jobs_dev, int njobs, uint32_t total_blocks, hipStream_t stream);
-int linear_x6r_fwd(const float *x, const void *wp, const float *bias, const float *residual, float *out, float *pre, int M, int N,
-                   int K, int act, int cfg, hipStream_t stream);
+int split_conv_weight_pair(const float *w, void *packed_fwd, void *packed_dx, int Co, int Ci, int ksize, hipStream_t stream);
 
 // ---- vit_gemm_sm.hip ----
 int linear_sm_set(int max_rows, int tm, int nw);

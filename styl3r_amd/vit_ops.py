@@ -40,7 +40,7 @@ from .weak_cache import WeakTensorCache
 _PKG = Path(__file__).resolve().parent
 _CSRC = _PKG / "csrc"
 LIB_PATH = _PKG / "lib" / os.environ.get("VIT_LIB_NAME", "libvit_hip.so")     # VIT_LIB_NAME: kernel-experiment builds (tools/ only); the product is libvit_hip.so
-_SOURCES = ["vit_rope.hip", "vit_attention.hip", "vit_attention_tail.hip", "vit_attention_bwd.hip", "vit_gemm.hip", "vit_attention_x6.hip", "vit_attention_bwd_x6.hip", "vit_gemm_x6.hip", "vit_gemm_sm.hip", "vit_gemm_x6r.hip", "vit_resample.hip", "vit_head_tail.hip", "vit_layernorm.hip", "vit_adapter.hip", "vit_optim.hip", "vit_snapshot.hip", "vit_lpips.hip", "vit_adaattn.hip", "vit_adain.hip", "vit_api.hip"]
+_SOURCES = ["vit_rope.hip", "vit_attention.hip", "vit_attention_tail.hip", "vit_attention_bwd.hip", "vit_gemm.hip", "vit_attention_x6.hip", "vit_attention_bwd_x6.hip", "vit_gemm_x6.hip", "vit_gemm_sm.hip", "vit_gemm_x6r.hip", "vit_weight_image.hip", "vit_resample.hip", "vit_head_tail.hip", "vit_layernorm.hip", "vit_adapter.hip", "vit_optim.hip", "vit_snapshot.hip", "vit_lpips.hip", "vit_adaattn.hip", "vit_adain.hip", "vit_api.hip"]
 EXPORTS = ("vit_rope2d", "vit_attention_fwd", "vit_attention_set_arith", "vit_attention_arith", "vit_attention_bwd", "vit_linear_fwd", "vit_split_weight_bytes",
            "vit_split_weight", "vit_x6_set_products", "vit_x6_products", "vit_x6_set_operand_amax", "vit_x6_set_output_amax", "vit_amax", "vit_split_weight_block_bytes", "vit_split_weight_block", "vit_split_weight_pair", "vit_split_conv_weight_pair", "vit_split_weights_many", "vit_linear_x6_fwd", "vit_linear_sm_set", "vit_linear_sm_ok", "vit_linear_sm_grouped", "vit_layernorm_fwd_grouped", "vit_linear_x6r_fwd", "vit_linear_x6c_fwd", "vit_linear_x6c_workspace_bytes", "vit_linear_x6c_choose_splits", "vit_linear_x6_wgrad", "vit_linear_x6_wgrad_acc", "vit_conv_x6_fwd", "vit_conv_x6_wgrad", "vit_upsample2x_fwd", "vit_upsample2x_bwd", "vit_relu_dropout_fwd", "vit_relu_dropout_bwd", "vit_layernorm_scratch_bytes", "vit_layernorm_fwd", "vit_layernorm_bwd",
            "vit_adapter_fwd", "vit_adapter_bwd", "vit_head_tail_fwd", "vit_head_tail_bwd", "vit_im2col7", "vit_im2col3_rows", "vit_upsample2x_add_relu_fwd", "vit_adamw_step", "vit_snapshot_chunk_bytes", "vit_snapshot_pack",
@@ -798,7 +798,7 @@ def refresh_split_cache(params) -> int:
                 if Kc % 8:
                     continue
                 packed = hit.payload
-                tail = packed.data_ptr() + ((R + 63) // 64 * 64 if block else R) * Kc * 6
+                tail = packed.data_ptr() + packed.numel() - 8192      # the |max| word closes the image (_image_buffer sized it by the library)
                 jobs.append((ptr, packed.data_ptr(), word.data_ptr() if word is not None else 0, tail, N, K,
                              (1 if transposed else 0) | (2 if block else 0), (Kc + 63) // 64, (R + 63) // 64))
                 entries.append((key, p, packed, word.data_ptr() if word is not None else 0))
@@ -861,7 +861,7 @@ def split_weight(weight: Tensor, transposed: bool = False) -> Tensor:
 
 
 def split_weight_block(weight: Tensor, transposed: bool = False) -> Tensor:
-    """bf16x3 split of a weight (N,K) in the BLOCK layout of csrc/vit_gemm_x6r.hip (vit_split_weight_block; rows padded to a
+    """bf16x3 split of a weight (N,K) in the BLOCK layout the ring kernels read (csrc/vit_weight_image.h; vit_split_weight_block; rows padded to a
     multiple of 64 with zeros).  Cached like `split_weight`."""
     return _linear_image(weight, True, transposed)
 

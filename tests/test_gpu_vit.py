@@ -239,10 +239,9 @@ def test_fused_linear_vs_fp64(M, N, K, gelu, res):
 # bf16x6 split arithmetic (csrc/vit_gemm_x6.hip): fp32 accuracy on the bf16 matrix cores
 # ---------------------------------------------------------------------------
 def _unpack_split(packed, rows, kcols):
-    """packed [rows][k/8][piece][8] bf16 -> three fp64 (rows, k) planes"""
-    raw = packed[: rows * kcols * 6].view(torch.int16).view(rows, kcols // 8, 3, 8).to(torch.int32)     # (8 KiB of trailing bytes: the f16x3 mode's |max| word)
-    f = (raw << 16).view(torch.float32)
-    return [f[:, :, p, :].reshape(rows, kcols).double() for p in range(3)]
+    """row-layout bf16 image -> three fp64 (rows, k) planes (tests/weight_image_cases.py)"""
+    from tests.weight_image_cases import unpack_image
+    return [p.to(packed.device) for p in unpack_image(packed, rows, kcols)]
 
 
 @pytest.mark.parametrize("transposed", [False, True])
