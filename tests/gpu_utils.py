@@ -77,3 +77,36 @@ def worst_row_rel(actual, expected, floor=1e-300):
     rel = err / den
     i = np.unravel_index(int(np.argmax(rel)), rel.shape)
     return float(rel[i]), (int(i[0]), int(i[2]), int(i[1]))
+
+
+CANCEL_FLOOR = 2.0 ** -8        # the two floors of tests/test_gpu_attention_ranges.py, for the 2-D row metric below
+RANGE_FLOOR = 2.0 ** -24
+
+
+def row_scales(expected, terms=None, tensor_max=None):
+    """what each row of a 2-D tensor is judged against: its own max |e|, but at least CANCEL_FLOOR x the row max of `terms` (the product
+    |a| . |b|^T of the contraction that made it: a row that is a near-complete cancellation) and at least RANGE_FLOOR x the tensor's maximum
+    (`tensor_max`, default max |expected|: a row far below anything the output's fp32 consumer can see).  Returns (scale per row, rows that
+    sit on a floor)."""
+    e = np.abs(np.asarray(expected, dtype=np.float64))
+    own = e.max(-1)
+    floor = np.full(own.shape, RANGE_FLOOR * (float(e.max()) if tensor_max is None else float(tensor_max)))
+    if terms is not None:
+        floor = np.maximum(floor, CANCEL_FLOOR * np.abs(np.asarray(terms, dtype=np.float64)).max(-1))
+    floor = np.maximum(floor, 1e-300)
+    return np.maximum(own, floor), own < floor
+
+
+def worst_row_rel_2d(actual, expected, terms=None, tensor_max=None, rows=None):
+    """per-ROW error of a 2-D (rows, columns) tensor: error of a row = max |a - e| over the row / max |e| over the row, with the two floors of
+    `row_scales`.  rows: judge only these (an index array or slice; the floors still come from the whole tensor).  A NaN / Inf counts as an
+    infinite error.  Returns (worst error, index of that row in the whole tensor)."""
+    a = np.asarray(actual, dtype=np.float64); e = np.asarray(expected, dtype=np.float64)
+    assert a.shape == e.shape and e.ndim == 2, (a.shape, e.shape)
+    with np.errstate(invalid="ignore", over="ignore"):
+        err = np.abs(a - e).max(-1)
+    err = np.where(np.isfinite(err), err, np.inf)
+    rel = err / row_scales(e, terms, tensor_max)[0]
+    idx = np.arange(e.shape[0])[rows] if rows is not None else np.arange(e.shape[0])
+    i = int(idx[int(np.argmax(rel[idx]))])
+    return float(rel[i]), i

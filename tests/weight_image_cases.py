@@ -51,6 +51,17 @@ def _pieces(values, mode, amax_word):
     return torch.stack([p0.view(torch.int16), p1.view(torch.int16), p2.view(torch.int16)], -1)
 
 
+def piece_planes(values, mode, amax_word=None):
+    """the pieces of `_pieces` as float64 planes of the shape of `values`, in the units of `values` (f16x3: two planes, divided by the exact
+    power-of-two scale again; bf16: three) -- for ANY operand of a split-arithmetic product: an activation's pieces are made by the same
+    rule from the |max| word announced for it (csrc/vit_common.h), so `amax_word` is whatever word the launch would be handed"""
+    p = _pieces(values, mode, amax_word)
+    if mode == "f16x3":
+        s = f16_scale_of(word_slots(amax_word).max())
+        return [p[..., i].contiguous().view(torch.float16).double() / s for i in range(2)]
+    return [(p[..., i].to(torch.int32) << 16).view(torch.float32).double() for i in range(3)]
+
+
 def expected_image(values, block, mode, amax_word=None):
     """the exact uint8 body (the piece bytes, without the |max| word) of the image of `values` (R, Kc)"""
     assert mode in MODES and values.dim() == 2 and values.shape[1] % 8 == 0
